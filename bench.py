@@ -12,8 +12,11 @@ N > 1, or --config cfg4 (2.0M Gaussians x 300 timestamps) at any N:
     the ranks (RCCL over xGMI, overlapping the next frame).  Views / timestamps shard round-robin over the ranks (i = r mod N),
     parameters are replicated; per-rank work is fixed as N grows (weak scaling), `value` = ms per frame of the whole job.
 `--gpus N` without a torchrun environment starts the N ranks itself (one process per GPU).  Rank 0 prints ONE JSON line.
-Extra legs outside the timed region: per-stage hipEvent timing (roofline) and, on rank 0 at N=1, the CPU baselines (the C oracle on
-BASELINE config 2 at full size and on a bounded sample of config 3, the pure-PyTorch rasterize of config 1).
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`).  `--full` adds the extra legs outside the
+timed region: the per-step distribution (`step_ms`), per-stage hipEvent timing (roofline), scene statistics, the secondary legs of the
+training core and of N > 1 runs, and, on rank 0 at N=1, the training-iteration timings (`model_step`) and the CPU baselines (the C oracle
+on BASELINE config 2 at full size and on a bounded sample of config 3, the pure-PyTorch rasterize of config 1).
+`--dump-outputs DIR` writes what the last timed step computed (outputs and gradients) to DIR/<name>.npy, for comparing two builds.
 """
 import argparse
 import json
@@ -308,9 +311,7 @@ def percentiles(ms):
 
 def timed_loop(step, steps, warmup, sync_all, finish=None):
     """W warm-up steps, then EXACTLY K timed steps between barrier + synchronize pairs -- nothing but the steps inside the timed region
-    (round 6: the per-step hipEvents of rounds 2-5 sat inside it, one marker packet per step on the op's stream).  The per-step
-    distribution (`step_ms`) comes from a SECOND loop of the same K steps with an event recorded after every step, outside the timed
-    region."""
+    (round 6: the per-step hipEvents of rounds 2-5 sat inside it, one marker packet per step on the op's stream).  Returns ms per step."""
     for i in range(warmup):
         step(i)
     if finish:
@@ -322,7 +323,12 @@ def timed_loop(step, steps, warmup, sync_all, finish=None):
     if finish:
         finish()
     sync_all()
-    t1 = time.perf_counter()
+    return 1e3 * (time.perf_counter() - t0) / max(steps, 1)
+
+
+def step_distribution(step, steps, sync_all, finish=None):
+    """The per-step distribution (`step_ms`, --full): a SECOND loop of the same K steps with an event recorded after every step, outside
+    the timed region."""
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
     ev[0].record()
     for i in range(steps):
@@ -331,8 +337,47 @@ def timed_loop(step, steps, warmup, sync_all, finish=None):
     if finish:
         finish()
     sync_all()
-    per_step = [ev[i].elapsed_time(ev[i + 1]) for i in range(steps)]
-    return 1e3 * (t1 - t0) / max(steps, 1), per_step
+    return [ev[i].elapsed_time(ev[i + 1]) for i in range(steps)]
+
+
+DUMP_BYTES = 64 * 10 ** 6      # --dump-outputs: at most this many bytes in all
+DUMP_ROWS = 16384              # arrays with more leading rows (per-Gaussian outputs) keep this fixed, seeded subset of their rows
+
+
+def fixed_sample(n, k):
+    """k indices into range(n), sorted: the same ones for every array of n rows / elements and in every run."""
+    g = torch.Generator().manual_seed(n)
+    idx = torch.randperm(n, generator=g)[:k] if n <= 1 << 24 else torch.randint(0, n, (k,), generator=g)
+    return idx.sort().values
+
+
+def dump_outputs(out_dir, arrays):
+    """{name: tensor} -> out_dir/<name>.npy: floats as float32, integers as float64 (exact); per-Gaussian arrays reduced to DUMP_ROWS
+    fixed rows; if that is still more than DUMP_BYTES, every array of more than 2^20 elements keeps the same fixed fraction of its
+    (flattened) elements."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    out = {}
+    for name, t in arrays.items():
+        if t is None or t.numel() == 0:
+            continue
+        t = t.detach()
+        if t.dim() and t.shape[0] > DUMP_ROWS:
+            t = t[fixed_sample(t.shape[0], DUMP_ROWS).to(t.device)]
+        exact = t.dtype in (torch.float64, torch.int32, torch.int64)
+        out[name] = t.to(torch.float64 if exact else torch.float32)
+    nbytes = lambda t: t.numel() * t.element_size()
+    total = sum(nbytes(t) for t in out.values())
+    if total > DUMP_BYTES:
+        big = [k for k, t in out.items() if t.numel() > 2 ** 20]
+        rest = total - sum(nbytes(out[k]) for k in big)
+        assert big and rest < DUMP_BYTES, f"--dump-outputs: {rest} bytes of small arrays alone exceed {DUMP_BYTES}"
+        frac = (DUMP_BYTES - rest) / (total - rest)
+        for k in big:
+            t = out[k].reshape(-1)
+            out[k] = t[fixed_sample(t.numel(), int(t.numel() * frac)).to(t.device)]
+    for name, t in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
 
 
 def main():
@@ -340,13 +385,18 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true", help="everything beside the headline: per-step distribution, per-stage timing and roofline, "
+                                                        "scene statistics, secondary legs (N > 1 exchange / wire probe, training core without "
+                                                        "optimizer), training-iteration timings and CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy "
+                                                                        "(float32 / float64, at most 64 MB: per-Gaussian arrays as a fixed row sample)")
     ap.add_argument("--config", default="cfg3", choices=sorted(CONFIGS))
     ap.add_argument("--points", type=int, default=None, help="override the Gaussian count (parity/debug only)")
     ap.add_argument("--fwd-asm", type=int, default=None, choices=[0, 1], help="tuning: compositing forward with the hand-scheduled entry walk (1, default) or the compiler's loop (0)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full runs: skip the CPU baselines")
     ap.add_argument("--no-allreduce", action="store_true", help="N > 1 without the gradient exchange (pure replicas)")
     ap.add_argument("--forward-only", action="store_true", help="render only (BASELINE config 5 is quoted as forward-only FPS); not the headline metric")
-    ap.add_argument("--no-model-step", action="store_true", help="skip the training-iteration timings (profiling runs)")
+    ap.add_argument("--no-model-step", action="store_true", help="--full runs: skip the training-iteration timings (profiling runs)")
     ap.add_argument("--train-core", action="store_true", help="N = 1: time the training-iteration core (what N > 1 and cfg4 time) instead of the rasterizer alone")
     ap.add_argument("--optimizer", default=None, choices=["none", "replicated", "sharded"],
                     help="training-core steps (N > 1, cfg4, --train-core): the optimizer step of the iteration.  Default: replicated -- the "
@@ -401,7 +451,7 @@ def main():
     # headline down with it); `--train-leg` adds a short leg of the training core itself with its exchange.
     train_mode = (args.config == "cfg4" or args.train_core) and not args.forward_only
     train_leg = world > 1 and not train_mode and not args.forward_only and args.train_leg
-    wire_probe = world > 1 and not train_mode and not args.forward_only
+    wire_probe = world > 1 and not train_mode and not args.forward_only and args.full
     if args.optimizer is None:
         # N >= 4: reduce-scatter + sharded RAdam (row-sharded keyframe windows) + all-gather -- half the bytes per link of the all-reduce
         # and 1/N of the optimizer's HBM stream per rank; N < 4: the replicated optimizer
@@ -417,10 +467,12 @@ def main():
             torch.distributed.barrier()
         torch.cuda.synchronize()
 
-    def run_train_core(steps, warmup):
+    def run_train_core(steps, warmup, primary):
         """The training-iteration core, one view per rank per step (N > 1: with the gradient exchange); returns its timings and, for the
-        statistics pass of a run whose PRIMARY step it is, the frames it rendered."""
+        statistics pass of a run whose PRIMARY step it is, the frames it rendered.  The secondary timings (without optimizer / exchange)
+        are taken by --full runs and by the secondary leg."""
         multi = None
+        extras = args.full or not primary
         # ---------------- training-iteration core, one view per rank per step ----------------
         from ex4dgs_amd.trainer import FrameTrainer
         model, cam, bg = make_scene(args.config, P=args.points, device=dev, fused=True)
@@ -438,29 +490,41 @@ def main():
                           lrs={n: 1e-7 for n in model.PARAM_NAMES},       # tiny learning rates: the synthetic scene stays put
                           async_forward=(True if (args.async_forward and kv == 1 and exchange == "none") else False), views_per_step=kv)
 
-        def step(i):
-            return tr.step(cam, bg, my_stamps[i % len(my_stamps)], upstream, near=cfg.min_depth, far=cfg.max_depth)["render"]
+        last = {}
 
-        ms_wall, per_step = timed_loop(step, steps, warmup, sync_all, finish=tr.flush)
+        def step(i):
+            out = tr.step(cam, bg, my_stamps[i % len(my_stamps)], upstream, near=cfg.min_depth, far=cfg.max_depth)
+            if dumping:
+                last["out"] = out
+            return out["render"]
+
+        dumping = primary and args.dump_outputs is not None
+        ms_wall = timed_loop(step, steps, warmup, sync_all, finish=tr.flush)
+        if dumping:
+            dumping = False
+            outs = {k: v for k, v in last["out"].items() if torch.is_tensor(v)}
+            outs.update({"param" + n: p for n, p in zip(model.PARAM_NAMES, model.parameters())})      # after the last step's optimizer update
+            dump_outputs(args.dump_outputs, outs)
+        per_step = step_distribution(step, steps, sync_all, finish=tr.flush) if args.full else None
         parallelism = f"views/timestamps sharded i = r (mod {world}), parameters replicated" + (
             "" if tr.exchange is None else (" + reduce-scatter / sharded RAdam / all-gather" if exchange == "sharded" else " + async RCCL all-reduce of the 15 model-parameter gradients"))
         step_what = (("" if kv == 1 else f"[{kv} views per rank and optimizer step, gradients accumulated locally, one exchange per {kv} views] ") +
                      "training-iteration core of one view per rank: fused attribute evaluation -> rasterizer forward+backward -> attribute "
                      "backward" + ("" if tr.exchange is None else " -> gradient exchange") + ("" if args.optimizer == "none" else f" -> {args.optimizer} RAdam step"))
         secondary = {}
-        if args.optimizer != "none":
+        if extras and args.optimizer != "none":
             # secondary number: the same step without the optimizer (the mode in which the exchange can hide behind the next frame)
             trn = FrameTrainer(model, exchange=("none" if exchange == "sharded" else exchange), optimizer=False)
             stepn = lambda i: trn.step(cam, bg, my_stamps[i % len(my_stamps)], upstream, near=cfg.min_depth, far=cfg.max_depth)
-            ms_noopt, _ = timed_loop(stepn, steps, max(2, warmup // 2), sync_all, finish=trn.flush)
+            ms_noopt = timed_loop(stepn, steps, max(2, warmup // 2), sync_all, finish=trn.flush)
             secondary["ms_per_step_without_optimizer"] = round(xdist.allreduce_max_scalar(ms_noopt, device=dev), 4)
             del trn
-        if world > 1:
+        if extras and world > 1:
             # the same loop (same optimizer) without the exchange (exposed communication = difference) and the exchange alone (its full length)
             tr0 = FrameTrainer(model, exchange="none", optimizer=(args.optimizer != "none"), sliced=(False if args.dense_keyframe_grads else None),
                                lrs={n: 1e-7 for n in model.PARAM_NAMES})
             step0 = lambda i: tr0.step(cam, bg, my_stamps[i % len(my_stamps)], upstream, near=cfg.min_depth, far=cfg.max_depth)
-            ms_noex, _ = timed_loop(step0, steps, max(2, warmup // 2), sync_all, finish=tr0.flush)
+            ms_noex = timed_loop(step0, steps, max(2, warmup // 2), sync_all, finish=tr0.flush)
             ex_alone = None
             if tr.exchange is not None and exchange == "allreduce":
                 trg = FrameTrainer(model, exchange="none")
@@ -471,7 +535,7 @@ def main():
 
                 def ex_only(i):
                     tr.exchange_feat.launch(gfeat); tr.exchange.launch(grest); tr.exchange_feat.wait(); tr.exchange.wait()
-                ex_alone, _ = timed_loop(ex_only, max(4, steps // 4), 2, sync_all)
+                ex_alone = timed_loop(ex_only, max(4, steps // 4), 2, sync_all)
             ms_noex_local = ms_noex
             ms_noex = xdist.allreduce_max_scalar(ms_noex, device=dev)
             # ranks that really took part: a sum all-reduce of ones over the process group (RCCL on the GPU backend), not the configured size
@@ -495,9 +559,11 @@ def main():
             multi["exposed_exchange_ms_per_step"] = round(max(0.0, ms_step - multi["ms_per_step_without_exchange"]), 4)
             if multi["allreduce_ms_per_step"] is not None:
                 multi["overlapped_exchange_ms_per_step"] = round(max(0.0, multi["allreduce_ms_per_step"] - multi["exposed_exchange_ms_per_step"]), 4)
-        model.fused = False           # plain getters for the statistics pass below (one [P,16,3] SH tensor instead of the SplitSH)
-        frames = [frame_inputs(model, t, dev) for t in my_stamps[:2]]
-        settings = tr._settings(cam, bg, cfg.min_depth, cfg.max_depth)
+        frames = settings = None
+        if primary and args.full:
+            model.fused = False           # plain getters for the statistics pass below (one [P,16,3] SH tensor instead of the SplitSH)
+            frames = [frame_inputs(model, t, dev) for t in my_stamps[:2]]
+            settings = tr._settings(cam, bg, cfg.min_depth, cfg.max_depth)
         return dict(ms_wall=ms_wall, ms_step=ms_step, per_step=per_step, multi=multi, secondary=secondary, parallelism=parallelism, step_what=step_what,
                     frames=frames, settings=settings, P=P, my_stamps=my_stamps)
 
@@ -521,6 +587,10 @@ def main():
         means2D = [torch.zeros(P, 3, device=dev, requires_grad=True) for _ in frames]
         dir3D = [torch.zeros(P, 3, device=dev, requires_grad=True) for _ in frames]
 
+        out_names = ("color", "radii", "depth", "flow", "acc", "idx")
+        grad_names = ("grad_means3D", "grad_shs", "grad_opacities", "grad_scales", "grad_rotations", "grad_means2D", "grad_dir3D")
+        last_step = {}
+
         def step(i):
             f = i % len(frames)
             xyz, shs, opa, scl, rot = frames[f]
@@ -528,10 +598,24 @@ def main():
                 t.grad = None
             if args.forward_only:
                 with torch.no_grad():
-                    return rasterize_gaussians(xyz, means2D[f], dir3D[f], shs, empty, opa, scl, rot, empty, settings)[0]
+                    outs = rasterize_gaussians(xyz, means2D[f], dir3D[f], shs, empty, opa, scl, rot, empty, settings)
+                if dumping:
+                    last_step.update(dict(zip(out_names, outs)))
+                return outs[0]
             color, radii, depth, flow, acc, idx = rasterize_gaussians(xyz, means2D[f], dir3D[f], shs, empty, opa, scl, rot, empty, settings)
             torch.autograd.backward([color, depth, flow, acc], [grads[0], grads[1], grads[2], grads[3]])
+            if dumping:
+                last_step.update(dict(zip(out_names, (color, radii, depth, flow, acc, idx))), frame=f)
             return color
+
+        def dump_last():
+            """--dump-outputs of the rasterizer step: its outputs and the gradients of its inputs in the last timed step"""
+            outs = {k: v for k, v in last_step.items() if k != "frame"}
+            if "frame" in last_step:
+                f = last_step["frame"]
+                outs.update({k: t.grad for k, t in zip(grad_names, frames[f] + [means2D[f], dir3D[f]]) if t.grad is not None})
+            dump_outputs(args.dump_outputs, outs)
+        dumping = args.dump_outputs is not None
 
         mode_note = ""
         if args.graph:
@@ -567,14 +651,24 @@ def main():
             def step(i):
                 graph.replay()
                 return gf[1]
-            ms_wall, per_step = timed_loop(step, args.steps, args.warmup, sync_all)
+            ms_wall = timed_loop(step, args.steps, args.warmup, sync_all)
+            if dumping:
+                last_step.update(dict(zip(out_names, (gf[1], gf[2], gf[6], gf[8], gf[7], gf[9]))))
+                if gb is not None:
+                    last_step.update(dict(zip(grad_names, (gb[3], gb[5], gb[2], gb[6], gb[7], gb[0], gb[8]))))
+                dump_last()
+            per_step = step_distribution(step, args.steps, sync_all) if args.full else None
             assert gf[0].wait().valid, "the captured frame overflowed its capacity"
             mode_note = f" replayed from one hipGraph (asynchronous forward, capacity {cap} for {gf[0].num_rendered} instances)"
         else:
             if args.async_frames:
                 from ex4dgs_amd.diff_gaussian_rasterization_df import async_frames
                 async_frames.enable(headroom=1.25, strict=False)
-            ms_wall, per_step = timed_loop(step, args.steps, args.warmup, sync_all)
+            ms_wall = timed_loop(step, args.steps, args.warmup, sync_all)
+            if dumping:
+                dumping = False
+                dump_last()
+            per_step = step_distribution(step, args.steps, sync_all) if args.full else None
             if args.async_frames:
                 async_frames.drain()
                 assert async_frames.invalid_frames == 0, "an asynchronous frame overflowed inside the timed region"
@@ -586,15 +680,15 @@ def main():
 
     secondary = {}
     if train_mode:
-        tc = run_train_core(args.steps, args.warmup)
+        tc = run_train_core(args.steps, args.warmup, primary=True)
         ms_wall, per_step, multi, secondary = tc["ms_wall"], tc["per_step"], tc["multi"], tc["secondary"]
         parallelism, step_what, frames, settings, P, my_stamps = tc["parallelism"], tc["step_what"], tc["frames"], tc["settings"], tc["P"], tc["my_stamps"]
         empty = torch.Tensor([])
-        means2D = [torch.zeros(P, 3, device=dev, requires_grad=True) for _ in frames]
-        dir3D = [torch.zeros(P, 3, device=dev, requires_grad=True) for _ in frames]
+        means2D = [torch.zeros(P, 3, device=dev, requires_grad=True) for _ in frames or ()]
+        dir3D = [torch.zeros(P, 3, device=dev, requires_grad=True) for _ in frames or ()]
     elif train_leg:
         # secondary leg of an N > 1 run: the training-iteration core with the RCCL exchange, a short loop -- NOT the line's `value`
-        tc = run_train_core(min(args.steps, 12), min(args.warmup, 3))
+        tc = run_train_core(min(args.steps, 12), min(args.warmup, 3), primary=False)
         multi = tc["multi"] or {}
         multi["train_core_ms_per_step"] = round(tc["ms_step"], 4)
         multi["train_core_ms_per_frame"] = round(tc["ms_step"] / world, 4)
@@ -632,86 +726,89 @@ def main():
 
     ms_per_step = xdist.allreduce_max_scalar(ms_wall, device=dev)
 
-    # ---- per-stage hipEvent timing of the rasterizer (outside the timed region), scene statistics ----------------
-    _C.profile_enable(True)
-    agg = {}
-    nprof = 12
-    for i in range(nprof):
-        f = i % len(frames)
-        xyz, shs, opa, scl, rot = frames[f]
-        for t in frames[f] + [means2D[f], dir3D[f]]:
-            t.grad = None
-        outs = rasterize_gaussians(xyz, means2D[f], dir3D[f], shs, empty, opa, scl, rot, empty, settings)
-        if not args.forward_only:
-            torch.autograd.backward([outs[0], outs[2], outs[3], outs[4]], grads)
-        torch.cuda.synchronize()
-        for which in (0, 1):
-            for name, ms in _C.profile_read(which):
-                agg[name] = agg.get(name, 0.0) + ms / nprof
-    _C.profile_enable(False)
-    last = _C.rasterize_gaussians(settings.bg, frames[0][0].detach(), empty, empty, frames[0][2].detach(), frames[0][3].detach(),
-                                  frames[0][4].detach(), 1.0, empty, settings.viewmatrix, settings.projmatrix, settings.tanfovx,
-                                  settings.tanfovy, 0.1, settings.subpixel_offset, H, W, frames[0][1].detach(), 3, settings.campos,
-                                  False, settings.min_depth, settings.max_depth, False)
-    R = int(last[0])
-    V = int((last[2] > 0).sum().item())
-    T = ((W + 15) // 16) * ((H + 15) // 16)
-    stage_bytes, A_fwd, A_bwd = algorithmic_bytes(P, V, R, H * W, T)
-    A = A_fwd + (0 if args.forward_only else A_bwd)
-    kernel_ms = sum(agg.values())
-    dom = max(agg, key=agg.get) if agg else None
-    dom_bytes = stage_bytes["sort"] if dom in ("tile_sort", "depth_sort") else stage_bytes.get(dom)
-    roof = None
-    traffic = valu_busy = valu_insts = frame_pmc = None
-    try:   # HBM bytes per launch from the rocprofv3 --pmc passes of this command, collected separately and committed (tools/pmc.sh)
-        with open(os.path.join(ROOT, PMC_FILE)) as fh:
-            pmc = json.load(fh)
-        pmc_ok = pmc_counters_current(pmc, dom)
-        if pmc_ok and args.config == "cfg3" and args.points is None and dom in pmc["kernels"]:
-            traffic = pmc["kernels"][dom]["hbm_bytes_per_launch"]
-            valu_busy = pmc["kernels"][dom].get("valu_busy_frac")
-            valu_insts = pmc["kernels"][dom].get("SQ_INSTS_VALU")
-        if pmc.get("frame") and pmc_counters_current(pmc, "frame") and args.config == "cfg3" and args.points is None and not args.forward_only:
-            frame_pmc = pmc["frame"]
-    except Exception:
-        traffic, pmc_ok = None, False
-    if dom is not None and dom_bytes:
-        achieved = dom_bytes / (agg[dom] * 1e-3) / 1e9
-        rast_ms = ms_per_step if not train_mode else kernel_ms
-        # What bounds the dominant kernel, from ITS counters: it is priced against HBM by the contract
-        # (`achieved` / `frac` below use the section-8(d) bytes of the reference's algorithm), but when its real HBM traffic is a small
-        # fraction of what the HBM could move in its duration and its SIMDs are busy issuing VALU instructions, the bound is the
-        # instruction issue: floor = wave-instructions x 4 cycles / (1024 SIMDs x 2.4 GHz)
-        issue_floor_ms = None if not valu_insts else valu_insts * 4.0 / (SIMDS * CLOCK_HZ) * 1e3
-        frac_traffic_dom = None if traffic is None else traffic / (agg[dom] * 1e-3) / 1e9 / HBM_PEAK_GBPS
-        bound = "hbm"
-        if valu_busy is not None and frac_traffic_dom is not None and valu_busy > 0.6 and frac_traffic_dom < 0.4:
-            bound = "valu-issue"
-        roof = {"bound": bound, "kernel": dom, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic,
-                "frac_traffic": None if frac_traffic_dom is None else round(frac_traffic_dom, 4),
-                "valu_insts": valu_insts, "issue_floor_ms": None if issue_floor_ms is None else round(issue_floor_ms, 4),
-                "frac_of_issue_floor": None if issue_floor_ms is None else round(issue_floor_ms / agg[dom], 4),
-                "note": ("achieved / frac: SURVEY 8(d) algorithmic bytes of the REFERENCE's algorithm / this kernel's duration (the contract's index); "
-                         "traffic / frac_traffic: this kernel's real HBM bytes per launch from the counters and their share of the 8 TB/s peak; "
-                         "bound: what its own counters say limits it"),
-                "traffic_source": (PMC_FILE + " (separate rocprofv3 --pmc passes of this command, committed with the hashes of the kernel sources; not re-measured in this run)")
-                                  if traffic is not None else (PMC_FILE + " is missing or was collected from other kernel sources (hash mismatch): no counter figure is quoted"),
-                "kernel_ms": round(agg[dom], 4), "algorithmic_bytes": int(dom_bytes),
-                # the kernel the contract prices against HBM is VALU-issue bound in practice: SQ counters of the committed PMC pass
-                "valu_busy_frac_pmc": valu_busy,
-                "frame": {"A_fwd_bytes": int(A_fwd), "A_bwd_bytes": int(A_bwd), "A_bytes": int(A),
-                          "achieved_GBps_walltime": round(A / (rast_ms * 1e-3) / 1e9, 1),
-                          "frac_walltime": round(A / (rast_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
-                          "achieved_GBps_kernels": round(A / (kernel_ms * 1e-3) / 1e9, 1) if kernel_ms > 0 else None,
-                          # the frame's REAL HBM traffic: counter bytes of every launch of one forward + backward, summed
-                          "hbm_traffic_bytes_pmc": None if frame_pmc is None else frame_pmc["hbm_bytes_per_frame"],
-                          "frac_traffic": None if frame_pmc is None else round(frame_pmc["hbm_bytes_per_frame"] / (rast_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
-                          "launches_pmc": None if frame_pmc is None else frame_pmc["launches_per_frame"],
-                          "valu_insts_pmc": None if frame_pmc is None else frame_pmc["SQ_INSTS_VALU_per_frame"],
-                          "issue_floor_ms": None if frame_pmc is None else round(frame_pmc["SQ_INSTS_VALU_per_frame"] * 4.0 / (SIMDS * CLOCK_HZ) * 1e3, 4)},
-                "stage_ms": {k: round(v, 4) for k, v in agg.items()},
-                "pair_evals_per_s_upper": round((1 if args.forward_only else 2) * 256.0 * R / (rast_ms * 1e-3), 0)}
+    # ---- --full: per-stage hipEvent timing of the rasterizer (outside the timed region), scene statistics ----------------
+    V = R = T = roof = None
+    if args.full:
+        _C.profile_enable(True)
+        agg = {}
+        nprof = 12
+        for i in range(nprof):
+            f = i % len(frames)
+            xyz, shs, opa, scl, rot = frames[f]
+            for t in frames[f] + [means2D[f], dir3D[f]]:
+                t.grad = None
+            outs = rasterize_gaussians(xyz, means2D[f], dir3D[f], shs, empty, opa, scl, rot, empty, settings)
+            if not args.forward_only:
+                torch.autograd.backward([outs[0], outs[2], outs[3], outs[4]], grads)
+            torch.cuda.synchronize()
+            for which in (0, 1):
+                for name, ms in _C.profile_read(which):
+                    agg[name] = agg.get(name, 0.0) + ms / nprof
+        _C.profile_enable(False)
+        last = _C.rasterize_gaussians(settings.bg, frames[0][0].detach(), empty, empty, frames[0][2].detach(), frames[0][3].detach(),
+                                      frames[0][4].detach(), 1.0, empty, settings.viewmatrix, settings.projmatrix, settings.tanfovx,
+                                      settings.tanfovy, 0.1, settings.subpixel_offset, H, W, frames[0][1].detach(), 3, settings.campos,
+                                      False, settings.min_depth, settings.max_depth, False)
+        R = int(last[0])
+        V = int((last[2] > 0).sum().item())
+        T = ((W + 15) // 16) * ((H + 15) // 16)
+        stage_bytes, A_fwd, A_bwd = algorithmic_bytes(P, V, R, H * W, T)
+        A = A_fwd + (0 if args.forward_only else A_bwd)
+        kernel_ms = sum(agg.values())
+        dom = max(agg, key=agg.get) if agg else None
+        dom_bytes = stage_bytes["sort"] if dom in ("tile_sort", "depth_sort") else stage_bytes.get(dom)
+        roof = None
+        traffic = valu_busy = valu_insts = frame_pmc = None
+        try:   # HBM bytes per launch from the rocprofv3 --pmc passes of this command, collected separately and committed (tools/pmc.sh)
+            with open(os.path.join(ROOT, PMC_FILE)) as fh:
+                pmc = json.load(fh)
+            pmc_ok = pmc_counters_current(pmc, dom)
+            if pmc_ok and args.config == "cfg3" and args.points is None and dom in pmc["kernels"]:
+                traffic = pmc["kernels"][dom]["hbm_bytes_per_launch"]
+                valu_busy = pmc["kernels"][dom].get("valu_busy_frac")
+                valu_insts = pmc["kernels"][dom].get("SQ_INSTS_VALU")
+            if pmc.get("frame") and pmc_counters_current(pmc, "frame") and args.config == "cfg3" and args.points is None and not args.forward_only:
+                frame_pmc = pmc["frame"]
+        except Exception:
+            traffic, pmc_ok = None, False
+        if dom is not None and dom_bytes:
+            achieved = dom_bytes / (agg[dom] * 1e-3) / 1e9
+            rast_ms = ms_per_step if not train_mode else kernel_ms
+            # What bounds the dominant kernel, from ITS counters: it is priced against HBM by the contract
+            # (`achieved` / `frac` below use the section-8(d) bytes of the reference's algorithm), but when its real HBM traffic is a small
+            # fraction of what the HBM could move in its duration and its SIMDs are busy issuing VALU instructions, the bound is the
+            # instruction issue: floor = wave-instructions x 4 cycles / (1024 SIMDs x 2.4 GHz)
+            issue_floor_ms = None if not valu_insts else valu_insts * 4.0 / (SIMDS * CLOCK_HZ) * 1e3
+            frac_traffic_dom = None if traffic is None else traffic / (agg[dom] * 1e-3) / 1e9 / HBM_PEAK_GBPS
+            bound = "hbm"
+            if valu_busy is not None and frac_traffic_dom is not None and valu_busy > 0.6 and frac_traffic_dom < 0.4:
+                bound = "valu-issue"
+            roof = {"bound": bound, "kernel": dom, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic,
+                    "frac_traffic": None if frac_traffic_dom is None else round(frac_traffic_dom, 4),
+                    "valu_insts": valu_insts, "issue_floor_ms": None if issue_floor_ms is None else round(issue_floor_ms, 4),
+                    "frac_of_issue_floor": None if issue_floor_ms is None else round(issue_floor_ms / agg[dom], 4),
+                    "note": ("achieved / frac: SURVEY 8(d) algorithmic bytes of the REFERENCE's algorithm / this kernel's duration (the contract's index); "
+                             "traffic / frac_traffic: this kernel's real HBM bytes per launch from the counters and their share of the 8 TB/s peak; "
+                             "bound: what its own counters say limits it"),
+                    "traffic_source": (PMC_FILE + " (separate rocprofv3 --pmc passes of this command, committed with the hashes of the kernel sources; not re-measured in this run)")
+                                      if traffic is not None else (PMC_FILE + " is missing or was collected from other kernel sources (hash mismatch): no counter figure is quoted"),
+                    "kernel_ms": round(agg[dom], 4), "algorithmic_bytes": int(dom_bytes),
+                    # the kernel the contract prices against HBM is VALU-issue bound in practice: SQ counters of the committed PMC pass
+                    "valu_busy_frac_pmc": valu_busy,
+                    "frame": {"A_fwd_bytes": int(A_fwd), "A_bwd_bytes": int(A_bwd), "A_bytes": int(A),
+                              "achieved_GBps_walltime": round(A / (rast_ms * 1e-3) / 1e9, 1),
+                              "frac_walltime": round(A / (rast_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
+                              "achieved_GBps_kernels": round(A / (kernel_ms * 1e-3) / 1e9, 1) if kernel_ms > 0 else None,
+                              # the frame's REAL HBM traffic: counter bytes of every launch of one forward + backward, summed
+                              "hbm_traffic_bytes_pmc": None if frame_pmc is None else frame_pmc["hbm_bytes_per_frame"],
+                              "frac_traffic": None if frame_pmc is None else round(frame_pmc["hbm_bytes_per_frame"] / (rast_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
+                              "launches_pmc": None if frame_pmc is None else frame_pmc["launches_per_frame"],
+                              "valu_insts_pmc": None if frame_pmc is None else frame_pmc["SQ_INSTS_VALU_per_frame"],
+                              "issue_floor_ms": None if frame_pmc is None else round(frame_pmc["SQ_INSTS_VALU_per_frame"] * 4.0 / (SIMDS * CLOCK_HZ) * 1e3, 4)},
+                    "stage_ms": {k: round(v, 4) for k, v in agg.items()},
+                    "pair_evals_per_s_upper": round((1 if args.forward_only else 2) * 256.0 * R / (rast_ms * 1e-3), 0)}
+
 
     if rank == 0:
         headline = args.config == "cfg3" and args.points is None and not train_mode and not args.forward_only
@@ -722,21 +819,23 @@ def main():
             "ms_per_step": round(ms_per_step, 4), "higher_is_better": False, "scaling": "weak", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic",
             "frames_per_s": round(1e3 * world / ms_per_step, 2),
-            "step_ms": percentiles(per_step),
-            "config": {"workload": cfg.name if args.points is None else f"{cfg.name} [P overridden to {P}]", "P": P, "V": V, "R": R,
-                       "HW": H * W, "tiles": T, "sh_degree": 3, "frames_per_step": world, "step": step_what, "parallelism": parallelism},
-            "roofline": roof,
+            "config": {"workload": cfg.name if args.points is None else f"{cfg.name} [P overridden to {P}]", "P": P,
+                       "HW": H * W, "sh_degree": 3, "frames_per_step": world, "step": step_what, "parallelism": parallelism},
         }
+        if args.full:
+            line["step_ms"] = percentiles(per_step)
+            line["config"].update(V=V, R=R, tiles=T)
+            line["roofline"] = roof
         if multi is not None:
             line["multi_gpu"] = multi
         elif train_mode and secondary:
             line["train_core"] = dict(optimizer=args.optimizer, **secondary)
-        if world == 1 and not args.no_model_step and not train_mode:
+        if args.full and world == 1 and not args.no_model_step and not train_mode:
             try:
                 line["model_step"] = model_step_timing(args.config, dev, grads, points=args.points)
             except Exception as e:
                 line["model_step"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 # the scalar C oracle on a bounded sample of this run's own workload ...
                 line["cpu_baseline"] = cpu_baseline(args.config, min(args.cpu_sample, P), my_stamps[0])

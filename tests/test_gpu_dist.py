@@ -296,7 +296,7 @@ def test_bench_spawns_its_ranks_itself(hip_lib, config):
     """`bench.py --gpus 2` without torchrun: the script starts both ranks (sharing the box's GPU over gloo), rank 0 prints ONE JSON
     line whose n_gpus is what was asked for, the collective carries the 15 model-parameter gradients."""
     cmd = [sys.executable, os.path.join(h.ROOT, "bench.py"), "--gpus", "2", "--share-device", "--backend", "gloo", "--config", config,
-           "--points", "20000", "--steps", "4", "--warmup", "2", "--no-cpu-baseline"] + (["--train-leg"] if config == "cfg3" else [])
+           "--points", "20000", "--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline"] + (["--train-leg"] if config == "cfg3" else [])
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]

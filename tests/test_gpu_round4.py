@@ -274,6 +274,39 @@ def test_bench_asynchronous_and_graph_modes_print_a_valid_line(hip_lib, mode):
     assert ("hipGraph" in d["config"]["step"]) if mode == "--graph" else ("asynchronous forward" in d["config"]["step"])
 
 
+def test_bench_plain_line_and_dumped_outputs(hip_lib, tmp_path):
+    """A plain `bench.py` run (no --full) prints the headline fields and nothing that needs runs of its own; `--dump-outputs` writes
+    what its last timed step computed as float32 / float64 arrays of at most 64 MB, and two runs with the same arguments agree: the
+    forward outputs bit for bit, the gradients to the order of the float atomics."""
+    import json, os, subprocess, sys
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    dumps = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        cmd = [sys.executable, os.path.join(h.ROOT, "bench.py"), "--gpus", "1", "--config", "cfg2", "--points", "20000", "--steps", "3",
+               "--warmup", "2", "--dump-outputs", str(out)]
+        r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["ms_per_step"] > 0 and d["value"] == d["ms_per_step"] and d["steps"] == 3 and d["unit"] == "ms/frame"
+        assert d["higher_is_better"] is False and d["dtype"] == "f32" and "GaussianRasterizer forward + backward" in d["config"]["step"]
+        assert not {"step_ms", "roofline", "model_step", "cpu_baseline"} & set(d), sorted(d)
+        arrays = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+        assert {"color", "depth", "acc", "radii", "grad_means3D", "grad_shs", "grad_opacities"} <= set(arrays), sorted(arrays)
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 * 10 ** 6
+        dumps.append(arrays)
+    a, b = dumps
+    assert a.keys() == b.keys()
+    for k in a:
+        if k.startswith("grad_"):
+            assert np.abs(a[k] - b[k]).max() <= 1e-3 * max(np.abs(a[k]).max(), 1e-30), k
+        else:
+            assert np.array_equal(a[k], b[k]), k
+
+
 def test_asynchronous_frames_soak_over_changing_views(hip_lib):
     """120 frames through the autograd surface under the asynchronous policy (strict: a truncated frame would raise), the timestamp and the
     camera distance changing from frame to frame so that the instance count moves by tens of percent, every frame's image and gradients

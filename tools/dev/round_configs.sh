@@ -6,7 +6,7 @@ root=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$root/gpurun_out
 mkdir -p $out
 cd $root
-B="--no-cpu-baseline --no-model-step"
+B="--full --no-cpu-baseline --no-model-step"
 timeout 300 python bench.py --config cfg2 $B > $out/${tag}_bench_cfg2.json 2> $out/${tag}_bench_cfg2.err
 timeout 300 python bench.py --config cfg2 $B --graph > $out/${tag}_bench_cfg2_graph.json 2> $out/${tag}_bench_cfg2_graph.err
 timeout 300 python bench.py $B --graph > $out/${tag}_bench_cfg3_graph.json 2> $out/${tag}_bench_cfg3_graph.err

@@ -1,6 +1,7 @@
 #!/bin/bash
 # usage (GPU box, repo root): tools/pmc.sh <tag> "<counter list>" [bench args]   -> gpurun_out/<tag>_pmc.db
 tag=$1; ctrs=$2; shift; shift
+set -- --full "$@"       # the profiled command is the full bench run (stage timers, roofline, step_ms)
 root=${GRAFT_REPO_ROOT:-$(pwd)}
 mkdir -p $root/gpurun_out
 cd /tmp && export TMPDIR=/tmp

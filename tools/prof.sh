@@ -2,6 +2,7 @@
 # usage (on the GPU box, from the repo root): tools/prof.sh <tag> [bench args...]
 # rocprofv3 kernel trace of a short bench run -> gpurun_out/<tag>_kernel_stats.txt
 tag=$1; shift
+set -- --full "$@"       # the profiled command is the full bench run (stage timers, roofline, step_ms)
 root=${GRAFT_REPO_ROOT:-$(pwd)}
 mkdir -p $root/gpurun_out
 cd /tmp && export TMPDIR=/tmp

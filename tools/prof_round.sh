@@ -20,7 +20,7 @@ run_pmc () {     # name, counters, command...
   rocprofv3 --kernel-trace --pmc $ctrs -d /tmp/pmc_$name -o $name -- "$@" > $out/${tag}_${name}_pmc.log 2>&1
   python $root/tools/pmc_summary.py $(find /tmp/pmc_$name -name "*.db" | head -1) > $out/${tag}_${name}.txt 2>&1
 }
-BENCH="python $root/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-model-step"
+BENCH="python $root/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-model-step"
 run_stats bench $BENCH
 grep '"metric"' $out/${tag}_bench.log > $out/${tag}_bench_under_rocprof.json
 run_pmc pmc_FETCH_SIZE "FETCH_SIZE" $BENCH
@@ -43,5 +43,5 @@ python tools/pmc_traffic.py $out/${tag}_pmc_FETCH_SIZE.txt $out/${tag}_pmc_WRITE
     $out/${tag}_iter_pmc_FETCH_SIZE.txt $out/${tag}_iter_pmc_WRITE_SIZE.txt $out/${tag}_iter_kernel_stats.txt $out/${tag}_knn_pmc_FETCH_SIZE.txt $out/${tag}_knn_pmc_WRITE_SIZE.txt $out/${tag}_knn_kernel_stats.txt | tail -60
 # the default bench line quotes these counters (bench.py: PMC_FILE, guarded by the kernel sources' hashes): put them where it looks
 cp $out/${tag}_pmc_traffic.json $root/profiles/${tag}_pmc_traffic.json
-python bench.py > $out/${tag}_bench_default.json 2> $out/${tag}_bench_default.err
+python bench.py --full > $out/${tag}_bench_default.json 2> $out/${tag}_bench_default.err
 head -16 $out/${tag}_bench_kernel_stats.txt | cut -c1-70,161-250
