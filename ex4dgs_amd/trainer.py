@@ -338,6 +338,39 @@ class FrameTrainer:
             if self.side is not None:
                 torch.cuda.current_stream(self.device).wait_stream(self.side)
 
+    def begin_density_control(self):
+        """Before densify_and_prune / a prune (ex4dgs_amd.densify) replaces the model's tensors: settles a pending asynchronous frame and
+        DROPS the pending gradients without applying them -- train.py densifies before optimizer.step(), which then skips every replaced
+        parameter (no .grad): that iteration's update is lost and the step count does not advance."""
+        if self.mode != "none" or self.k != 1:
+            raise NotImplementedError("density control on a FrameTrainer needs exchange='none' and views_per_step=1: "
+                                      "multi-rank density control needs a reduction of the statistics first")
+        if self.async_forward:
+            self._settle_frame()
+        self.finish_exchange()
+        if self.side is not None:
+            torch.cuda.current_stream(self.device).wait_stream(self.side)
+        self._grads = None
+
+    def rebind_parameters(self, moments=None):
+        """After the model's tensors were replaced (ex4dgs_amd.densify): picks up the new parameters and rebuilds the P-sized buffers
+        (gradient buffers, keyframe slice gathers).  moments: {name: (exp_avg, exp_avg_sq)} remapped to the new rows (None: zeros)."""
+        if self._grads is not None:
+            raise RuntimeError("rebind_parameters: pending gradients (call begin_density_control first)")
+        self.params = [getattr(self.model, n) for n in self.names]
+        self.pgrad = [None if i in self.feature_idx else torch.zeros_like(p) for i, p in enumerate(self.params)]
+        if self.sliced:
+            self.kf_gather = []
+            for i in self.kf_idx:
+                shape = (self.params[i].shape[0],) + attr.SLICED_SHAPES[self.names[i]]
+                self.pgrad[i] = torch.zeros(shape, dtype=torch.float32, device=self.device)
+                self.kf_gather.append(xdist.SliceGather(shape, self.device, local_only=True))
+        if self.optimizer:
+            moments = moments or {}
+            pairs = [moments.get(n) for n in self.names]
+            self.m = [pr[0] if pr is not None else torch.zeros_like(p) for pr, p in zip(pairs, self.params)]
+            self.v = [pr[1] if pr is not None else torch.zeros_like(p) for pr, p in zip(pairs, self.params)]
+
     def grads(self):
         """The 15 (summed) parameter gradients of the last frame, valid after flush() when no optimizer consumed them."""
         return dict(zip(self.names, self._grads)) if self._grads is not None else None

@@ -1,0 +1,136 @@
+/*
+ * ex4d_densify.h -- C ABI of adaptive density control: per-iteration densification statistics, the clone / split / prune
+ * classification with its compaction, and one multi-tensor gather that builds the new parameter, moment and statistic tensors.
+ *
+ * Restates scene/c_gaussian_model.py of the reference: add_densification_stats (:1095), mark_prune_stats (:1105),
+ * add_l1_ssim_stats (:1119), densify_and_clone (:966), densify_and_split (:874), densification_postfix (:789-844),
+ * densify_and_prune (:1019), prune_invisible (:1074), prune_small (:1087), prune_nan_points (:1229) and the optimizer-state
+ * edits of _prune_optimizer / cat_tensors_to_optimizer (:700-787).  DESIGN.md section 7 lists the quirks kept.
+ *
+ * A model has two groups: static rows (g = 0) and dynamic rows (g = 1).  The statistics of a group are ONE float32 block
+ * [EX4D_DENSIFY_STATS, n] (structure of arrays), row order EX4D_STAT_*.  The caller owns all memory; every call takes a
+ * hipStream_t and never synchronises it.
+ */
+#ifndef EX4D_DENSIFY_H_INCLUDED
+#define EX4D_DENSIFY_H_INCLUDED
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define EX4D_DENSIFY_STATS 9
+enum {
+    EX4D_STAT_GRAD_ACCUM = 0,    /* xyz_gradient_accum / motion_xyz_gradient_accum            init 0 */
+    EX4D_STAT_DENOM = 1,         /* denom / motion_denom                                      init 0 */
+    EX4D_STAT_ERROR_ACCUM = 2,   /* xyz_error_accum / motion_xyz_error_mean                   init 0 */
+    EX4D_STAT_SSIM_ACCUM = 3,    /* xyz_ssim_error_accum / motion_xyz_ssim_error_accum        init 0 */
+    EX4D_STAT_ERROR_DENOM = 4,   /* error_denom / motion_error_denom                          init 0 */
+    EX4D_STAT_MAX_RADII = 5,     /* max_radii2D / motion_max_radii2D                          init 0 */
+    EX4D_STAT_MIN_RADII = 6,     /* min_radii2D / motion_min_radii2D                          init 1000 */
+    EX4D_STAT_ERROR_MIN = 7,     /* xyz_error_min / motion_xyz_error_min                      init 1000 */
+    EX4D_STAT_ERROR_MIN_T = 8    /* xyz_error_min_timestamp / motion_xyz_error_min_timestamp  init -1 */
+};
+
+/* ---- per-iteration statistics: one thread per row, no atomics, no host synchronisation (graph-capturable) */
+#define EX4D_DENSIFY_PRUNE_STATS 1     /* mark_prune_stats: filter e0 > 0, min_radii = min(min_radii, radii) */
+#define EX4D_DENSIFY_GRAD_STATS 2      /* the `iteration < densify_until_iter` block: filter radii > 0, max_radii, add_densification_stats */
+#define EX4D_DENSIFY_L1_STATS 4        /* ... and add_l1_ssim_stats inside that block */
+
+/* stats_s [9, ns], stats_d [9, nd] (may be NULL when nd == 0); radii int32 [ns + nd]; vgrad = dL/dmeans2D float [ns + nd, 3];
+ * egrad = the error channels (e0, e1, e2) float [ns + nd, 3], may be NULL when neither PRUNE_STATS nor L1_STATS is set. */
+int ex4d_densify_stats(float *stats_s, int64_t ns, float *stats_d, int64_t nd, const int32_t *radii, const float *vgrad,
+                       const float *egrad, float timestamp, int32_t flags, void *stream);
+
+/* ---- classification + compaction of one group */
+enum { EX4D_PLAN_DENSIFY = 0, EX4D_PLAN_PRUNE_INVISIBLE = 1, EX4D_PLAN_PRUNE_SMALL = 2, EX4D_PLAN_PRUNE_NAN = 3 };
+
+/* counts[] written by ex4d_densify_plan (device int32 [EX4D_PLAN_COUNTS]) */
+enum {
+    EX4D_CNT_KEEP = 0,           /* surviving original rows */
+    EX4D_CNT_CLONE_SEL = 1,      /* rows selected for clone (= clone jitter draws) */
+    EX4D_CNT_KEEP_CLONE = 2,     /* surviving clones */
+    EX4D_CNT_SPLIT_SEL = 3,      /* original rows selected for split */
+    EX4D_CNT_SPLIT_SEL_CLONE = 4,/* clones selected for split (only through the max_screen_size terms) */
+    EX4D_CNT_KEEP_CHILD = 5,     /* surviving children per copy, of split originals */
+    EX4D_CNT_KEEP_CHILD_CLONE = 6,/* ... of split clones */
+    EX4D_CNT_ROWS = 7            /* rows after the call: KEEP + KEEP_CLONE + 2 (KEEP_CHILD + KEEP_CHILD_CLONE) */
+};
+#define EX4D_PLAN_COUNTS 8
+#define EX4D_PLAN_MAP_INTS 8     /* per source row: dst_orig, dst_clone, dst_child (copy 0, of the row), dst_child_of_clone (copy 0),
+                                    clone draw, split draw, split draw of the clone, unused; -1 = none */
+
+typedef struct Ex4dDensifyPlanGroup {
+    int64_t n;                   /* rows of the group (0: the call does nothing for it) */
+    const float *stats;          /* device [9, n] */
+    const float *scaling;        /* device [n, 3]: log scales (DENSIFY) */
+    const float *opacity;        /* device [n]: opacity logits (DENSIFY) */
+    const float *xyz;            /* device [n, xyz_width] (PRUNE_NAN: any NaN in the row prunes it) */
+    int32_t xyz_width;
+    int32_t use_screen;          /* max_screen_size (static) / max_dynamic_screen_size (dynamic) was given */
+    float grad_thr;              /* max_grad / max_dgrad */
+    float dense_scale;           /* percent_dense * extent (float32, as torch compares) */
+    float big_scale;             /* 0.1 * extent */
+    float screen_size;
+    float min_opacity;
+    float l1_thres;
+    float max_ssim;
+    int32_t reserved;
+    int32_t *map;                /* device [n, EX4D_PLAN_MAP_INTS] (written) */
+    int32_t *counts;             /* device [EX4D_PLAN_COUNTS] (written) */
+    void *scratch;               /* device, ex4d_densify_scratch_bytes(n) */
+} Ex4dDensifyPlanGroup;
+
+size_t ex4d_densify_scratch_bytes(int64_t n);
+int ex4d_densify_plan(int32_t mode, const Ex4dDensifyPlanGroup *group, void *stream);
+
+/* ---- the multi-tensor gather.  For every source row with a map entry >= 0 the kernel writes that destination row; what a
+ * new row (clone / child) holds is the descriptor's rule.  A surviving original row is always a copy, except for the reset
+ * statistic rows of EX4D_RULE_STATS. */
+enum {
+    EX4D_RULE_COPY = 0,          /* every destination copies the source row (parameters, and every tensor of a prune) */
+    EX4D_RULE_ZERO_NEW = 1,      /* new rows 0 (exp_avg, exp_avg_sq) */
+    EX4D_RULE_CONST_NEW = 2,     /* new rows = value (_opacity_duration_var: 2) */
+    EX4D_RULE_CHILD_SCALING = 3, /* children log(exp(s) / (0.8 N)) */
+    EX4D_RULE_CHILD_XYZ = 4,     /* children R(normalize(q_k)) (sigma exp(s) * z) + x_k per keyframe k; aux0 = rotations [n, K, 4], aux1 = log scales [n, 3] */
+    EX4D_RULE_CENTER = 5,        /* clones and children: duration centres jittered by len * z and clamped (children of clones: twice) */
+    EX4D_RULE_STATS = 6          /* a [9, n] statistics block after densification_postfix */
+};
+
+typedef struct Ex4dDensifyTensor {
+    const float *src;
+    float *dst;
+    int64_t rows;                /* source rows */
+    int64_t dst_rows;            /* destination rows (plane stride of a statistics block) */
+    int32_t width;               /* floats per row */
+    int32_t planes;              /* 1, or EX4D_DENSIFY_STATS for a statistics block */
+    int32_t rule;
+    int32_t group;               /* 0 static, 1 dynamic: which Ex4dDensifyApplyGroup */
+    const float *aux0, *aux1;
+    float value;                 /* EX4D_RULE_CONST_NEW; EX4D_RULE_CHILD_XYZ: sigma (1 static, 2 dynamic) */
+    int32_t reserved;
+} Ex4dDensifyTensor;
+
+typedef struct Ex4dDensifyApplyGroup {
+    const int32_t *map;          /* device [rows, EX4D_PLAN_MAP_INTS] from ex4d_densify_plan */
+    int64_t child_stride;        /* KEEP_CHILD + KEEP_CHILD_CLONE: destination distance of copy 1 from copy 0 */
+    int64_t n_split;             /* SPLIT_SEL + SPLIT_SEL_CLONE: draw distance of copy 1 from copy 0 */
+    const float *split_z;        /* device [2 n_split, 3] standard normal: split samples, copy-major */
+    const float *split_c1, *split_c0;   /* device [2 n_split]: children's centre jitter (c1 drawn first) */
+    const float *clone_c1, *clone_c0;   /* device [CLONE_SEL]: clones' centre jitter */
+    float min_len;               /* 2 / interval */
+    float center_lo, center_hi;  /* (time_shift + 1) / interval, (time_shift + duration - 1) / interval */
+    float split_div;             /* 0.8 N */
+} Ex4dDensifyApplyGroup;
+
+#define EX4D_DENSIFY_MAX_TENSORS 24
+int ex4d_densify_apply(const Ex4dDensifyTensor *tensors, int32_t count, const Ex4dDensifyApplyGroup *groups, void *stream);
+
+const char *ex4d_densify_last_error(void);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

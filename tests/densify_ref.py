@@ -1,0 +1,192 @@
+"""Device-agnostic torch restatement of the reference's adaptive density control (scene/c_gaussian_model.py:715-1145, :1229 and
+train.py:199-216), with explicit random draws: the checker of ex4dgs_amd.densify, pinned itself by tests/golden/densify.npz.
+
+State: {"params": {name: tensor}, "m": {name: tensor} | None, "v": ..., "stats": {reference stat name: tensor}} with the
+reference's shapes ([N, 1] statistics, [N] radii).  Draws: the keys of ex4dgs_amd.densify._draws.
+"""
+import torch
+
+STATIC = ("_xyz", "_xyz_disp", "_rotation", "_opacity", "_scaling", "_features_dc", "_features_rest")
+DYNAMIC = ("_xyz_motion", "_rotation_motion", "_opacity_motion", "_opacity_duration_center", "_opacity_duration_var", "_scaling_motion",
+           "_features_dc_motion", "_features_rest_motion")
+S_STATS = ("xyz_gradient_accum", "denom", "xyz_error_accum", "xyz_ssim_error_accum", "error_denom", "max_radii2D", "min_radii2D",
+           "xyz_error_min", "xyz_error_min_timestamp")
+D_STATS = ("motion_xyz_gradient_accum", "motion_denom", "motion_xyz_error_mean", "motion_xyz_ssim_error_accum", "motion_error_denom",
+           "motion_max_radii2D", "motion_min_radii2D", "motion_xyz_error_min", "motion_xyz_error_min_timestamp")
+INIT = (0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1000.0, 1000.0, -1.0)
+
+
+def init_stats(ns, nd, device="cpu"):
+    out = {}
+    for names, n in ((S_STATS, ns), (D_STATS, nd)):
+        for k, v in zip(names, INIT):
+            shape = (n,) if k.endswith("radii2D") else (n, 1)
+            out[k] = torch.full(shape, v, dtype=torch.float32, device=device)
+    return out
+
+
+def update(st, radii, vgrad, egrad, timestamp, densify_stats=True, prune_stats=True, l1_accum=True):
+    """train.py:199-216 on the statistics dict `st` (in place)."""
+    ns = st["xyz_gradient_accum"].shape[0]
+    halves = ((slice(0, ns), S_STATS), (slice(ns, None), D_STATS))
+    for sl, names in halves:
+        if st[names[0]].shape[0] == 0:
+            continue
+        r, g = radii[sl], vgrad[sl]
+        if l1_accum and prune_stats and egrad is not None:                 # mark_prune_stats (:1105)
+            vis = egrad[sl][:, 0] > 0
+            st[names[6]][vis] = torch.min(st[names[6]][vis], r[vis])
+        if not densify_stats:
+            continue
+        vis = r > 0
+        st[names[5]][vis] = torch.max(st[names[5]][vis], r[vis])
+        st[names[0]][vis] += torch.norm(g[vis, :2], dim=-1, keepdim=True)     # add_densification_stats (:1095)
+        st[names[1]][vis] += 1
+        if l1_accum and egrad is not None:                                   # add_l1_ssim_stats (:1119)
+            e = egrad[sl]
+            l1 = e[vis, 1:2] / e[vis, 0:1].clamp_min(1e-4)
+            hit = torch.logical_and(st[names[7]][vis] > l1, e[vis, 0:1] > 0.01)
+            st[names[8]][vis] = torch.where(hit, timestamp * torch.ones_like(l1), st[names[8]][vis])
+            st[names[7]][vis] = torch.where(hit, l1, st[names[7]][vis])
+            st[names[2]][vis] += l1
+            st[names[3]][vis] += e[vis, 2:3] / e[vis, 0:1].clamp_min(1e-4)
+            st[names[4]][vis] += (e[vis, 0:1] > 0).float()
+
+
+def _rot(r):
+    norm = torch.sqrt(r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1] + r[:, 2] * r[:, 2] + r[:, 3] * r[:, 3])
+    q = r / norm[:, None]
+    R = torch.zeros((q.size(0), 3, 3), device=r.device)
+    r, x, y, z = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+    R[:, 0, 0] = 1 - 2 * (y * y + z * z); R[:, 0, 1] = 2 * (x * y - r * z); R[:, 0, 2] = 2 * (x * z + r * y)
+    R[:, 1, 0] = 2 * (x * y + r * z); R[:, 1, 1] = 1 - 2 * (x * x + z * z); R[:, 1, 2] = 2 * (y * z - r * x)
+    R[:, 2, 0] = 2 * (x * z - r * y); R[:, 2, 1] = 2 * (y * z + r * x); R[:, 2, 2] = 1 - 2 * (x * x + y * y)
+    return R
+
+
+def _jitter(c, z1, z0, model):
+    c = c.clone()
+    ln = ((c[:, 1] - c[:, 0]).abs() / 3).clamp_min(2 / model["interval"])
+    c[:, 1] = c[:, 1] + ln * z1.view(-1, 1)
+    c[:, 0] = c[:, 0] + ln * z0.view(-1, 1)
+    return c.clamp((model["time_shift"] + 1) / model["interval"], (model["time_shift"] + model["duration"] - 1) / model["interval"])
+
+
+def _cat(state, names, stat_names, new, n_new):
+    """densification_postfix (:789-844): parameters + zero moments appended, statistics reset except error min / timestamp."""
+    P, st = state["params"], state["stats"]
+    for k in names:
+        P[k] = torch.cat([P[k], new[k]])
+        for mk in ("m", "v"):
+            if state.get(mk) is not None:
+                state[mk][k] = torch.cat([state[mk][k], torch.zeros_like(new[k])])
+    n = P[names[0]].shape[0]
+    for k, v in zip(stat_names[:7], INIT[:7]):
+        st[k] = torch.full((n,) if k.endswith("radii2D") else (n, 1), v, device=P[names[0]].device)
+
+
+def _gather(state, names, stat_names, keep):
+    P, st = state["params"], state["stats"]
+    for k in names:
+        P[k] = P[k][keep]
+        for mk in ("m", "v"):
+            if state.get(mk) is not None:
+                state[mk][k] = state[mk][k][keep]
+    for k in stat_names:
+        st[k] = st[k][keep]
+
+
+def densify_and_prune(state, model, max_grad, max_dgrad, min_opacity, min_motion_opacity, extent, max_screen_size, max_dynamic_screen_size,
+                      draws, s_max_ssim=0.5, s_l1_thres=0.1, d_max_ssim=0.5, d_l1_thres=0.1, percent_dense=0.01):
+    """model: {"interval", "time_shift", "duration"}.  Draws as ex4dgs_amd.densify._draws.  Returns the prune masks' survivors counts."""
+    P, st = state["params"], state["stats"]
+    has_d = P["_xyz_motion"].shape[0] > 0
+    grads = {}
+    for key, a, d in (("s", "xyz_gradient_accum", "denom"), ("d", "motion_xyz_gradient_accum", "motion_denom")):
+        g = st[a] / st[d]
+        g[g.isnan()] = 0.0
+        grads[key] = g
+    # ---- clone (:966)
+    sel_s = (torch.norm(grads["s"], dim=-1) >= max_grad) & (torch.exp(P["_scaling"]).max(dim=1).values <= percent_dense * extent)
+    new = {k: P[k][sel_s] for k in STATIC}
+    st["xyz_error_min"] = torch.cat([st["xyz_error_min"], st["xyz_error_min"][sel_s]])
+    st["xyz_error_min_timestamp"] = torch.cat([st["xyz_error_min_timestamp"], st["xyz_error_min_timestamp"][sel_s]])
+    _cat(state, STATIC, S_STATS, new, None)
+    if has_d:
+        sel_d = (torch.norm(grads["d"], dim=-1) >= max_dgrad) & (torch.exp(P["_scaling_motion"]).max(dim=1).values <= percent_dense * extent)
+        newd = {k: P[k][sel_d] for k in DYNAMIC}
+        newd["_opacity_duration_center"] = _jitter(newd["_opacity_duration_center"], draws["clone_c1"], draws["clone_c0"], model)
+        newd["_opacity_duration_var"] = torch.ones_like(newd["_opacity_duration_var"]) * 2
+        st["motion_xyz_error_min"] = torch.cat([st["motion_xyz_error_min"], st["motion_xyz_error_min"][sel_d]])
+        st["motion_xyz_error_min_timestamp"] = torch.cat([st["motion_xyz_error_min_timestamp"], st["motion_xyz_error_min_timestamp"][sel_d]])
+        _cat(state, DYNAMIC, D_STATS, newd, None)
+    # ---- split (:874), N = 2, over the post-clone set
+    N = 2
+    n0 = P["_xyz"].shape[0]
+    pad = torch.zeros(n0, device=P["_xyz"].device)
+    pad[:grads["s"].shape[0]] = grads["s"].squeeze(-1)
+    sc = torch.exp(P["_scaling"])
+    ss = (pad >= max_grad) & (sc.max(dim=1).values > percent_dense * extent)
+    if max_screen_size:
+        ss = ss | (st["max_radii2D"] > max_screen_size) | (sc.max(dim=1).values > 0.1 * extent)
+    samples = sc[ss].repeat(N, 1) * draws["static_split_z"]
+    new = {k: P[k][ss].repeat(N, *([1] * (P[k].dim() - 1))) for k in STATIC}
+    new["_xyz"] = torch.bmm(_rot(P["_rotation"][ss]).repeat(N, 1, 1), samples.unsqueeze(-1)).squeeze(-1) + P["_xyz"][ss].repeat(N, 1)
+    new["_scaling"] = torch.log(sc[ss].repeat(N, 1) / (0.8 * N))
+    prune_s = torch.cat([ss, torch.zeros(N * int(ss.sum()), dtype=torch.bool, device=ss.device)])
+    m = int(ss.sum()) * N
+    st["xyz_error_min"] = torch.cat([st["xyz_error_min"], torch.full((m, 1), 1000.0, device=ss.device)])
+    st["xyz_error_min_timestamp"] = torch.cat([st["xyz_error_min_timestamp"], torch.full((m, 1), -1.0, device=ss.device)])
+    if has_d:
+        n1 = P["_xyz_motion"].shape[0]
+        K = P["_xyz_motion"].shape[1]
+        padd = torch.zeros(n1, device=pad.device)
+        padd[:grads["d"].shape[0]] = grads["d"].squeeze(-1)
+        scd = torch.exp(P["_scaling_motion"])
+        sd = (padd >= max_dgrad) & (scd.max(dim=1).values > percent_dense * extent)
+        if max_dynamic_screen_size:
+            sd = sd | (st["motion_max_radii2D"] > max_dynamic_screen_size) | (scd.max(dim=1).values > 0.1 * extent)
+        smp = (scd[sd].repeat(N, 1) * 2 * draws["split_z"]).unsqueeze(1).repeat(1, K, 1).view(-1, 3)
+        rots = _rot(P["_rotation_motion"][sd].view(-1, 4)).reshape(-1, K, 3, 3).repeat(N, 1, 1, 1).view(-1, 3, 3)
+        newd = {k: P[k][sd].repeat(N, *([1] * (P[k].dim() - 1))) for k in DYNAMIC}
+        newd["_xyz_motion"] = torch.bmm(rots, smp.unsqueeze(-1)).squeeze(-1).view(-1, K, 3) + P["_xyz_motion"][sd].repeat(N, 1, 1)
+        newd["_scaling_motion"] = torch.log(scd[sd].repeat(N, 1) / (0.8 * N))
+        newd["_opacity_duration_center"] = _jitter(newd["_opacity_duration_center"], draws["split_c1"], draws["split_c0"], model)
+        newd["_opacity_duration_var"] = torch.ones_like(newd["_opacity_duration_var"]) * 2
+        prune_d = torch.cat([sd, torch.zeros(N * int(sd.sum()), dtype=torch.bool, device=sd.device)])
+        md = int(sd.sum()) * N
+        st["motion_xyz_error_min"] = torch.cat([st["motion_xyz_error_min"], torch.full((md, 1), 1000.0, device=sd.device)])
+        st["motion_xyz_error_min_timestamp"] = torch.cat([st["motion_xyz_error_min_timestamp"], torch.full((md, 1), -1.0, device=sd.device)])
+        _cat(state, DYNAMIC, D_STATS, newd, None)
+    _cat(state, STATIC, S_STATS, new, None)
+    # ---- prune (:1034-1070): split originals + opacity + screen terms + the l1 / ssim masks on the reset statistics
+    ps = prune_s | (torch.sigmoid(P["_opacity"]) < min_opacity).squeeze(-1)
+    if max_screen_size:
+        ps = ps | (st["max_radii2D"] > max_screen_size) | (torch.exp(P["_scaling"]).max(dim=1).values > 0.1 * extent)
+    ps = ps | (st["xyz_error_accum"] / st["error_denom"].clamp(1e-4) > s_l1_thres).squeeze(-1)
+    ssim = st["xyz_ssim_error_accum"] / st["error_denom"].clamp(1e-4)
+    ps = ps | ((ssim < s_max_ssim) * (ssim > 0)).squeeze(-1)
+    _gather(state, STATIC, S_STATS, ~ps)
+    if has_d:
+        pd = prune_d | (torch.sigmoid(P["_opacity_motion"]) < min_motion_opacity).squeeze(-1)
+        pd = pd | (st["motion_xyz_error_mean"] / st["motion_error_denom"].clamp(1e-4) > d_l1_thres).squeeze(-1)
+        ssd = st["motion_xyz_ssim_error_accum"] / st["motion_error_denom"].clamp(1e-4)
+        pd = pd | ((ssd < d_max_ssim) * (ssd > 0)).squeeze(-1)
+        if max_dynamic_screen_size:
+            pd = pd | (st["motion_max_radii2D"] > max_dynamic_screen_size) | (torch.exp(P["_scaling_motion"]).max(dim=1).values > 0.1 * extent)
+        _gather(state, DYNAMIC, D_STATS, ~pd)
+
+
+def prune(state, kind):
+    """kind: "invisible" (:1074), "small" (:1087), "nan" (:1229)."""
+    P, st = state["params"], state["stats"]
+    if kind == "invisible":
+        ms, md = st["xyz_error_min_timestamp"].squeeze(-1) < 0, st["motion_xyz_error_min_timestamp"].squeeze(-1) < 0
+    elif kind == "small":
+        ms, md = st["min_radii2D"] < 5, st["motion_min_radii2D"] < 5
+    else:
+        ms = P["_xyz"].isnan().any(dim=-1)
+        md = P["_xyz_motion"].isnan().flatten(start_dim=1).any(dim=-1)
+    _gather(state, STATIC, S_STATS, ~ms)
+    if P["_xyz_motion"].shape[0] > 0:
+        _gather(state, DYNAMIC, D_STATS, ~md)
