@@ -30,6 +30,7 @@ SOURCES = {
     "ex4d_optim.hip": ["-ffp-contract=off"],
     "ex4d_knn.hip": ["-ffp-contract=off"],
     "ex4d_densify.hip": ["-ffp-contract=off"],      # density control: threshold decisions and copied values follow torch's float32 ops
+    "ex4d_regularizers.hip": ["-ffp-contract=off"], # motion regularisers: the gradient arithmetic is shared bit for bit with ex4d_optim.hip
     "ex4d_trainer.hip": [],          # host code only: the compiled host path of one training iteration (include/ex4d_trainer.h)
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fno-fast-math", "-Wall", "-Wno-unused-function"]
@@ -110,7 +111,8 @@ def build(force=False, verbose=False, extra_flags=()):
     hipcc = _hipcc()
     headers = [os.path.join(CSRC, "ex4d_internal.h"), os.path.join(HERE, "..", "include", "ex4d_rasterizer.h"),
                os.path.join(HERE, "..", "include", "ex4d_attributes.h"), os.path.join(HERE, "..", "include", "ex4d_loss.h"), os.path.join(HERE, "..", "include", "ex4d_optim.h"), os.path.join(HERE, "..", "include", "ex4d_knn.h"), os.path.join(HERE, "..", "include", "ex4d_trainer.h"),
-               os.path.join(HERE, "..", "include", "ex4d_densify.h"),
+               os.path.join(HERE, "..", "include", "ex4d_densify.h"), os.path.join(HERE, "..", "include", "ex4d_regularizers.h"),
+               os.path.join(CSRC, "ex4d_reg_rows.h"),
                os.path.abspath(__file__)]
     objs = []
     for src, flags in SOURCES.items():

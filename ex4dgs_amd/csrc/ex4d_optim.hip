@@ -6,6 +6,7 @@
 // HBM-bound streaming: 16-byte loads/stores, 4096-element chunks, a chunk table in kernel arguments maps workgroups to
 // tensors.  ffp-contract is off for this file: the update follows torch's op order in float32.
 #include "ex4d_internal.h"
+#include "ex4d_reg_rows.h"
 #include "../../include/ex4d_optim.h"
 #include <cmath>
 #include <cstdio>
@@ -149,6 +150,114 @@ __global__ __launch_bounds__(256) void radam_sliced_kernel(const SlicedArgs a)
     }
 }
 
+// ---- keyframe tensors with windowed gradients PLUS a motion regulariser formed from the row itself (train.py:159-168)
+// motion_reg / rot_reg make the gradient dense over all K keyframes, but it is a function of the Gaussian's own row: keyframe k needs
+// the PRE-update keyframe 0 (motion) or k-1, k+1 (rotation).  So a workgroup owns whole rows -- a block of R rows = one contiguous span
+// of R K C floats (R a multiple of 4: 16-byte aligned for odd K C) -- stages p in LDS with 16-byte loads, forms the regulariser gradient
+// of every slice from the LDS copy into a second LDS array, then streams p (from LDS), m, v with 16-byte accesses like the kernels
+// above: 24 B per element plus the windows, the dense gradient never exists in memory.
+#define REG_LDS_BYTES 32768       // p copy + regulariser gradient of one block of rows: five workgroups per CU
+struct RegSlot {
+    SlicedSlot t;            // first_block: this tensor's first workgroup
+    long long rows;
+    int kind;                // ex4d_reg::KIND_*
+    int R;                   // rows per workgroup
+    float coef;              // weight / (Nd (K-1))
+};
+struct RegArgs { RegSlot slot[EX4D_RADAM_MAX_SLICED]; int count; };
+
+static int reg_block_rows(int K, int C)
+{
+    const long long per_row = 2LL * K * C * (long long)sizeof(float);
+    long long R = REG_LDS_BYTES / per_row;
+    R = R > 32 ? 32 : R & ~3LL;
+    return (int)R;           // 0: four rows do not fit
+}
+
+__global__ __launch_bounds__(256) void radam_sliced_reg_kernel(const RegArgs a)
+{
+    extern __shared__ float4 lds4[];
+    int ti = 0;
+#pragma unroll 1
+    for (int i = 1; i < a.count; i++) if (blockIdx.x >= a.slot[i].t.first_block) ti = i;
+    const RegSlot &rs = a.slot[ti];
+    const SlicedSlot &s = rs.t;
+    const int K = s.K, C = s.C, KC = K * C;
+    const long long row0 = (long long)(blockIdx.x - s.first_block) * rs.R;
+    const int nrows = (int)(rs.rows - row0 < rs.R ? rs.rows - row0 : rs.R);
+    const int n = nrows * KC;                              // floats of this workgroup's span (<= R K C <= REG_LDS_BYTES / 8)
+    const long long base = row0 * KC;
+    float *p = s.s.p + base, *m = s.s.m + base, *v = s.s.v + base;
+    float *P = (float *)lds4, *G = P + rs.R * KC;          // R K C is a multiple of 4: G stays 16-byte aligned
+    const bool vec = (n & 3) == 0 && ((((uintptr_t)p | (uintptr_t)m | (uintptr_t)v) & 15) == 0);
+    const bool reg = rs.kind != ex4d_reg::KIND_NONE;
+    int first[EX4D_RADAM_MAX_WINDOWS];
+#pragma unroll
+    for (int w = 0; w < EX4D_RADAM_MAX_WINDOWS; w++) first[w] = (s.first_dev && w < s.nw) ? s.first_dev[w] : s.first[w];
+
+    if (vec) for (int i = threadIdx.x; i < n / 4; i += 256) ((float4 *)P)[i] = ((const float4 *)p)[i];
+    else for (int i = threadIdx.x; i < n; i += 256) P[i] = p[i];
+    __syncthreads();
+    if (reg) {
+        // one thread per (row, keyframe) slice: odd stride 3 (conflict-free) or one 16-byte LDS access per keyframe
+        const int slices = nrows * K;
+        if (rs.kind == ex4d_reg::KIND_MOTION) {
+            for (int sl = threadIdx.x; sl < slices; sl += 256) {
+                const int r = sl / K, k = sl - r * K;
+                if (k == 0) continue;
+                float g[3];
+                ex4d_reg::motion_grad(P + r * KC, K, k, rs.coef, g);
+                G[sl * 3] = g[0]; G[sl * 3 + 1] = g[1]; G[sl * 3 + 2] = g[2];
+            }
+            __syncthreads();
+            // keyframe 0: the sum of the K-1 unit vectors (= minus the entries just written) in ascending k, the order of motion_grad
+            for (int r = threadIdx.x; r < nrows; r += 256) {
+                float *g = G + r * KC;
+                float x = 0.f, y = 0.f, z = 0.f;
+                for (int k = 1; k < K; k++) { x += -g[3 * k]; y += -g[3 * k + 1]; z += -g[3 * k + 2]; }
+                g[0] = x; g[1] = y; g[2] = z;
+            }
+        } else {
+            for (int sl = threadIdx.x; sl < slices; sl += 256) {
+                const int r = sl / K, k = sl - r * K;
+                float g[4];
+                ex4d_reg::rot_grad(P + r * KC, K, k, rs.coef, g);
+                ((float4 *)G)[sl] = make_float4(g[0], g[1], g[2], g[3]);
+            }
+        }
+        __syncthreads();
+    }
+    if (vec) {
+        for (int i = threadIdx.x; i < n / 4; i += 256) {
+            const int e = 4 * i;
+            int sl = e / C;
+            int c = e - sl * C;
+            int r = sl / K;
+            int kk = sl - r * K;
+            float g[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                g[j] = sliced_grad(s, first, row0 + r, kk, c);
+                if (++c == C) { c = 0; if (++kk == K) { kk = 0; r++; } }
+            }
+            if (reg) { const float4 gg = ((const float4 *)G)[i]; g[0] += gg.x; g[1] += gg.y; g[2] += gg.z; g[3] += gg.w; }
+            float4 pp = ((const float4 *)P)[i], mm = ((float4 *)m)[i], vv = ((float4 *)v)[i];
+            radam_update(pp.x, g[0], mm.x, vv.x, s.s); radam_update(pp.y, g[1], mm.y, vv.y, s.s);
+            radam_update(pp.z, g[2], mm.z, vv.z, s.s); radam_update(pp.w, g[3], mm.w, vv.w, s.s);
+            ((float4 *)p)[i] = pp; ((float4 *)m)[i] = mm; ((float4 *)v)[i] = vv;
+        }
+    } else {
+        for (int i = threadIdx.x; i < n; i += 256) {
+            const int sl = i / C, r = sl / K;
+            float g = sliced_grad(s, first, row0 + r, sl - r * K, i - sl * C);
+            if (reg) g += G[i];
+            float pp = P[i], mm = m[i], vv = v[i];
+            radam_update(pp, g, mm, vv, s.s);
+            p[i] = pp; m[i] = mm; v[i] = vv;
+        }
+    }
+}
+
 thread_local char g_optim_err[256] = "";
 
 static bool fill_coefficients(RadamSlot &s, double lr, long long step, double beta1, double beta2, double eps)
@@ -241,6 +350,77 @@ int ex4d_radam_step_sliced(const Ex4dRadamSlicedTensor *tensors, int32_t count, 
     }
     if (blocks == 0) return EX4D_OK;
     hipLaunchKernelGGL(radam_sliced_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { snprintf(g_optim_err, sizeof(g_optim_err), "launch failed: %s", hipGetErrorString(e)); return EX4D_ERR_HIP; }
+    return EX4D_OK;
+}
+
+int32_t ex4d_radam_sliced_reg_rows(int32_t K, int32_t C)
+{
+    if (K < 1 || (C != 3 && C != 4)) return 0;
+    return reg_block_rows(K, C);
+}
+
+int ex4d_radam_step_sliced_reg(const Ex4dRadamSlicedRegTensor *tensors, int32_t count, double beta1, double beta2, double eps, void *stream_)
+{
+    g_optim_err[0] = 0;
+    if (count < 0 || count > EX4D_RADAM_MAX_SLICED || (count > 0 && !tensors)) {
+        snprintf(g_optim_err, sizeof(g_optim_err), "count %d outside [0, %d]", count, EX4D_RADAM_MAX_SLICED);
+        return EX4D_ERR_ARG;
+    }
+    RegArgs a;
+    a.count = 0;
+    unsigned blocks = 0;
+    size_t lds = 0;
+    for (int i = 0; i < count; i++) {
+        const Ex4dRadamSlicedTensor &t = tensors[i].t;
+        const int kind = tensors[i].reg_kind;
+        if (t.rows == 0) continue;
+        if (t.rows < 0 || t.K < 1 || (t.C != 3 && t.C != 4) || t.step < 1 || !t.param || !t.exp_avg || !t.exp_avg_sq ||
+            t.n_windows < 0 || t.n_windows > EX4D_RADAM_MAX_WINDOWS) {
+            snprintf(g_optim_err, sizeof(g_optim_err), "sliced tensor %d: bad shape, step < 1, null pointer or too many windows", i);
+            return EX4D_ERR_ARG;
+        }
+        if (kind < 0 || kind > 2 || (kind == ex4d_reg::KIND_MOTION && t.C != 3) || (kind == ex4d_reg::KIND_ROT && t.C != 4) ||
+            (kind != 0 && tensors[i].reg_rows < t.rows)) {
+            snprintf(g_optim_err, sizeof(g_optim_err), "sliced tensor %d: reg_kind %d does not fit C = %d, or reg_rows < rows", i, kind, t.C);
+            return EX4D_ERR_ARG;
+        }
+        RegSlot &r = a.slot[a.count];
+        r.R = reg_block_rows(t.K, t.C);
+        if (r.R < 4) {
+            snprintf(g_optim_err, sizeof(g_optim_err), "sliced tensor %d: four rows of K = %d keyframes do not fit the %d bytes of LDS a workgroup stages "
+                     "(dense gradients + ex4d_reg_backward + ex4d_radam_step take any K)", i, t.K, REG_LDS_BYTES);
+            return EX4D_ERR_ARG;
+        }
+        a.count++;
+        SlicedSlot &s = r.t;
+        s.s.p = t.param; s.s.g = nullptr; s.s.m = t.exp_avg; s.s.v = t.exp_avg_sq; s.s.numel = t.rows * t.K * t.C; s.s.first_chunk = 0; s.s.sanitize = 0;
+        s.first_dev = t.first_dev;
+        fill_coefficients(s.s, t.lr, t.step, beta1, beta2, eps);
+        s.slices = t.rows * t.K; s.K = t.K; s.C = t.C; s.nw = t.n_windows;
+        for (int w = 0; w < EX4D_RADAM_MAX_WINDOWS; w++) {
+            const bool live = w < t.n_windows;
+            if (live && (((t.first[w] < 0 || t.first[w] + t.count[w] > t.K) && !t.first_dev) || t.count[w] < 1 || t.count[w] > t.K || !t.grad[w])) {
+                snprintf(g_optim_err, sizeof(g_optim_err), "sliced tensor %d: window %d outside [0, K) or null", i, w);
+                return EX4D_ERR_ARG;
+            }
+            s.first[w] = live ? t.first[w] : 0; s.count[w] = live ? t.count[w] : 0; s.grad[w] = live ? t.grad[w] : nullptr;
+        }
+        // the mean's constant on the host in double; a term with nothing to average (K = 1) or weight 0 is a plain sliced step
+        const double pairs = (double)tensors[i].reg_rows * (t.K - 1);
+        r.coef = (kind != 0 && pairs > 0) ? (float)(tensors[i].reg_weight / pairs) : 0.f;
+        r.kind = r.coef != 0.f ? kind : ex4d_reg::KIND_NONE;
+        r.rows = t.rows;
+        s.first_block = blocks;
+        const long long nb = (t.rows + r.R - 1) / r.R;
+        if (nb + blocks > 0x7fffffffLL) { snprintf(g_optim_err, sizeof(g_optim_err), "too many elements for one launch"); return EX4D_ERR_ARG; }
+        blocks += (unsigned)nb;
+        const size_t need = 2 * (size_t)r.R * t.K * t.C * sizeof(float);
+        lds = need > lds ? need : lds;
+    }
+    if (blocks == 0) return EX4D_OK;
+    hipLaunchKernelGGL(radam_sliced_reg_kernel, dim3(blocks), dim3(256), lds, (hipStream_t)stream_, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { snprintf(g_optim_err, sizeof(g_optim_err), "launch failed: %s", hipGetErrorString(e)); return EX4D_ERR_HIP; }
     return EX4D_OK;

@@ -12,6 +12,7 @@
 #include "../../include/ex4d_loss.h"
 #include "../../include/ex4d_optim.h"
 #include "../../include/ex4d_rasterizer.h"
+#include "../../include/ex4d_regularizers.h"
 #include "../../include/ex4d_trainer.h"
 
 namespace {
@@ -77,6 +78,10 @@ struct Ex4dTrainer {
     Ex4dFrameStatus *status = nullptr;
     hipEvent_t status_ev = nullptr;
     int64_t replays = 0;
+    // motion regularisers (ex4d_trainer_set_regularizers): weights of the next steps, their float[4] output, the forward's scratch
+    double reg_w[3] = { 0.0, 0.0, 0.0 };
+    float *reg_out = nullptr;
+    double *reg_scratch = nullptr;
     void *owned[96] = {};
     int n_owned = 0;
 
@@ -149,6 +154,7 @@ Ex4dTrainer *ex4d_trainer_create(const Ex4dTrainerConfig *cfg, float *const *par
         ok = t->take(reinterpret_cast<unsigned char *&>(s), ex4d_backward_scratch_bytes(t->P));
         t->bwd_scratch = s;
     }
+    ok = ok && t->take(t->reg_out, 4, true) && t->take(t->reg_scratch, ex4d_reg_scratch_bytes() / sizeof(double));
     if (ok) {
         const float one = 1.0f;
         ok = hipMemcpy(t->grad_loss, &one, sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
@@ -264,16 +270,27 @@ int ex4d_trainer_step(Ex4dTrainer *t, double timestamp, const float *viewmatrix,
         t->replays++;
     }
 
+    const bool reg = t->reg_w[0] != 0.0 || t->reg_w[1] != 0.0 || t->reg_w[2] != 0.0;
+    if (reg) {
+        // train.py:155-168: the three terms at this iteration's parameters; the L1/SSIM loss stays in loss[1]
+        if (ex4d_reg_forward(p[1], c.Ns, p[7], p[8], c.Nd, c.K, t->reg_w[0], t->reg_w[1], t->reg_w[2], t->reg_out, t->reg_scratch, stream))
+            return tfail(EX4D_ERR_HIP, "regularisers: %s", ex4d_reg_last_error());
+        // _xyz_disp's term joins its dense gradient; the keyframe terms are formed inside the sliced optimizer step below
+        if (c.optimizer && ex4d_reg_backward(p[1], g[1], c.Ns, nullptr, nullptr, nullptr, nullptr, 0, 1, t->reg_w[0], 0.0, 0.0, nullptr, 1, stream))
+            return tfail(EX4D_ERR_HIP, "regularisers: %s", ex4d_reg_last_error());
+    }
     if (c.optimizer) {
         t->step += 1;
         Ex4dRadamTensor dense[EX4D_TRAINER_PARAMS];
-        Ex4dRadamSlicedTensor sl[2];
+        Ex4dRadamSlicedRegTensor slr[2];
         int nd = 0, ns = 0;
         for (int i = 0; i < EX4D_TRAINER_PARAMS; i++) {
             if (t->numel[i] == 0) continue;
             if (i == 7 || i == 8) {
-                Ex4dRadamSlicedTensor &s = sl[ns++];
-                memset(&s, 0, sizeof(s));
+                Ex4dRadamSlicedRegTensor &sr = slr[ns++];
+                memset(&sr, 0, sizeof(sr));
+                Ex4dRadamSlicedTensor &s = sr.t;
+                sr.reg_kind = i == 7 ? 1 : 2; sr.reg_weight = t->reg_w[i == 7 ? 1 : 2]; sr.reg_rows = c.Nd;
                 s.param = p[i]; s.exp_avg = t->m[i]; s.exp_avg_sq = t->v[i]; s.rows = c.Nd; s.K = c.K; s.C = i == 7 ? 3 : 4;
                 s.lr = c.lr[i]; s.step = t->step; s.n_windows = 1;
                 s.first[0] = t->slices[i == 7 ? 0 : 2]; s.count[0] = t->slices[i == 7 ? 1 : 3]; s.grad[0] = g[i];
@@ -285,7 +302,13 @@ int ex4d_trainer_step(Ex4dTrainer *t, double timestamp, const float *viewmatrix,
             }
         }
         if (nd && ex4d_radam_step(dense, nd, c.beta1, c.beta2, c.eps, stream)) return tfail(EX4D_ERR_HIP, "RAdam: %s", ex4d_optim_last_error());
-        if (ns && ex4d_radam_step_sliced(sl, ns, c.beta1, c.beta2, c.eps, stream)) return tfail(EX4D_ERR_HIP, "RAdam (sliced): %s", ex4d_optim_last_error());
+        if (ns && reg) {
+            if (ex4d_radam_step_sliced_reg(slr, ns, c.beta1, c.beta2, c.eps, stream)) return tfail(EX4D_ERR_HIP, "RAdam (sliced, regularised): %s", ex4d_optim_last_error());
+        } else if (ns) {
+            Ex4dRadamSlicedTensor sl[2];
+            for (int i = 0; i < ns; i++) sl[i] = slr[i].t;
+            if (ex4d_radam_step_sliced(sl, ns, c.beta1, c.beta2, c.eps, stream)) return tfail(EX4D_ERR_HIP, "RAdam (sliced): %s", ex4d_optim_last_error());
+        }
     }
     return EX4D_OK;
 }
@@ -303,6 +326,19 @@ int ex4d_trainer_set_async(Ex4dTrainer *t, int32_t on)
 }
 
 int64_t ex4d_trainer_replays(const Ex4dTrainer *t) { return t ? t->replays : 0; }
+
+int ex4d_trainer_set_regularizers(Ex4dTrainer *t, double static_reg, double motion_reg, double rot_reg)
+{
+    t_err[0] = 0;
+    if (!t) return tfail(EX4D_ERR_ARG, "null argument");
+    if (!(static_reg >= 0.0) || !(motion_reg >= 0.0) || !(rot_reg >= 0.0)) return tfail(EX4D_ERR_ARG, "regulariser weight negative or NaN");
+    const bool on = static_reg != 0.0 || motion_reg != 0.0 || rot_reg != 0.0;
+    if (on && !t->cfg.optimizer) return tfail(EX4D_ERR_ARG, "regularisers join the gradients inside the optimizer step: the trainer was built without one");
+    if (on && t->cfg.Nd > 0 && (ex4d_radam_sliced_reg_rows(t->cfg.K, 3) == 0 || ex4d_radam_sliced_reg_rows(t->cfg.K, 4) == 0))
+        return tfail(EX4D_ERR_ARG, "K = %d keyframes do not fit the regularised sliced optimizer step", t->cfg.K);
+    t->reg_w[0] = static_reg; t->reg_w[1] = t->cfg.Nd > 0 ? motion_reg : 0.0; t->reg_w[2] = t->cfg.Nd > 0 ? rot_reg : 0.0;
+    return EX4D_OK;
+}
 
 int ex4d_trainer_set_lr(Ex4dTrainer *t, const double *lr15)
 {
@@ -333,6 +369,7 @@ const void *ex4d_trainer_output(const Ex4dTrainer *t, int32_t what)
     case 3: return t->g_means2D;
     case 4: return t->depth;
     case 5: return t->acc;
+    case 6: return t->reg_out;
     default: return nullptr;
     }
 }
@@ -354,8 +391,9 @@ int ex4d_trainer_read(const Ex4dTrainer *t, int32_t what, void *dst, size_t byte
     if (what >= 100 && what < 100 + EX4D_TRAINER_PARAMS) { src = t->grad[what - 100]; have = (size_t)t->grad_numel[what - 100] * sizeof(float); }
     else {
         src = ex4d_trainer_output(t, what);
-        const size_t sizes[6] = { sizeof(float), 3 * HW * sizeof(float), P * sizeof(int32_t), 3 * P * sizeof(float), HW * sizeof(float), HW * sizeof(float) };
-        if (what >= 0 && what < 6) have = sizes[what];
+        const size_t sizes[7] = { sizeof(float), 3 * HW * sizeof(float), P * sizeof(int32_t), 3 * P * sizeof(float), HW * sizeof(float), HW * sizeof(float),
+                                  4 * sizeof(float) };
+        if (what >= 0 && what < 7) have = sizes[what];
     }
     if (bytes > have || (bytes > 0 && !src)) return tfail(EX4D_ERR_ARG, "buffer %d holds %zu bytes, %zu requested", what, have, bytes);
     if (bytes && hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess)

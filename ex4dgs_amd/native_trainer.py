@@ -19,7 +19,7 @@ from .trainer import reference_lrs
 
 EXPORTS = ("ex4d_trainer_last_error", "ex4d_trainer_create", "ex4d_trainer_destroy", "ex4d_trainer_step", "ex4d_trainer_output",
            "ex4d_trainer_grad", "ex4d_trainer_read", "ex4d_trainer_bytes", "ex4d_trainer_time_scalars", "ex4d_trainer_set_lr",
-           "ex4d_trainer_set_sh_degree", "ex4d_trainer_set_async", "ex4d_trainer_replays")
+           "ex4d_trainer_set_sh_degree", "ex4d_trainer_set_async", "ex4d_trainer_replays", "ex4d_trainer_set_regularizers")
 
 
 class Ex4dTrainerConfig(C.Structure):
@@ -54,6 +54,8 @@ def _lib():
         lib.ex4d_trainer_set_sh_degree.argtypes = [C.c_void_p, C.c_int32]
         lib.ex4d_trainer_set_async.restype = C.c_int
         lib.ex4d_trainer_set_async.argtypes = [C.c_void_p, C.c_int32]
+        lib.ex4d_trainer_set_regularizers.restype = C.c_int
+        lib.ex4d_trainer_set_regularizers.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double]
         lib.ex4d_trainer_replays.restype = C.c_int64
         lib.ex4d_trainer_replays.argtypes = [C.c_void_p]
         lib.ex4d_trainer_bytes.restype = C.c_size_t
@@ -70,7 +72,8 @@ class NativeTrainer:
                  spatial_lr_scale=1.0):
         """lrs: per-parameter learning rates overriding the reference table (trainer.reference_lrs(spatial_lr_scale));
         near / far default to the reference's dataset.near / dataset.far (arguments/__init__.py:74-75).  This is the render +
-        L1/SSIM + RAdam core of the iteration (include/ex4d_trainer.h: SCOPE): no regularisers, no l1_accum hook, no densification."""
+        L1/SSIM + RAdam core of the iteration (include/ex4d_trainer.h: SCOPE): the motion regularisers are off until set_regularizers
+        gives them weights; no l1_accum hook, no densification."""
         self.model = model
         self.names = list(attr.PARAM_ORDER)
         self.params = [getattr(model, n) for n in self.names]
@@ -143,15 +146,24 @@ class NativeTrainer:
         if _lib().ex4d_trainer_set_async(self.handle, int(bool(on))):
             raise RuntimeError(_lib().ex4d_trainer_last_error().decode())
 
+    def set_regularizers(self, static_reg=0.0, motion_reg=0.0, rot_reg=0.0):
+        """Weights of the motion regularisers (train.py:155-168) from the next step on, as regularizers.regularizer_weights returns them
+        for the iteration (a 3-tuple as the first argument works too); all 0 = off.  output('reg') holds their values."""
+        if isinstance(static_reg, (tuple, list)):
+            static_reg, motion_reg, rot_reg = static_reg
+        if _lib().ex4d_trainer_set_regularizers(self.handle, float(static_reg), float(motion_reg), float(rot_reg)):
+            raise RuntimeError(_lib().ex4d_trainer_last_error().decode())
+
     def replays(self):
         return int(_lib().ex4d_trainer_replays(self.handle))
 
     def output(self, what):
-        """Copies of the trainer's outputs of the last step: 'loss', 'render', 'radii', 'viewspace_grad', 'depth', 'acc'."""
-        idx = {"loss": 0, "render": 1, "radii": 2, "viewspace_grad": 3, "depth": 4, "acc": 5}[what]
+        """Copies of the trainer's outputs of the last step: 'loss', 'render', 'radii', 'viewspace_grad', 'depth', 'acc', 'reg' (the
+        regularisers' three means and their weighted sum)."""
+        idx = {"loss": 0, "render": 1, "radii": 2, "viewspace_grad": 3, "depth": 4, "acc": 5, "reg": 6}[what]
         P = self.cfg.Ns + self.cfg.Nd
         shape, dtype = {0: ((1,), torch.float32), 1: ((3, self.H, self.W), torch.float32), 2: ((P,), torch.int32), 3: ((P, 3), torch.float32),
-                        4: ((1, self.H, self.W), torch.float32), 5: ((1, self.H, self.W), torch.float32)}[idx]
+                        4: ((1, self.H, self.W), torch.float32), 5: ((1, self.H, self.W), torch.float32), 6: ((4,), torch.float32)}[idx]
         return self._read(idx, shape, dtype)
 
     def grad(self, name):

@@ -13,7 +13,8 @@ import torch
 
 from . import _C
 
-EXPORTS = ("ex4d_optim_last_error", "ex4d_radam_step", "ex4d_radam_step_sliced")
+EXPORTS = ("ex4d_optim_last_error", "ex4d_radam_step", "ex4d_radam_step_sliced", "ex4d_radam_step_sliced_reg", "ex4d_radam_sliced_reg_rows")
+REG_NONE, REG_MOTION, REG_ROT = 0, 1, 2
 MAX_WINDOWS = 8
 MAX_SLICED = 4
 MAX_TENSORS = 32
@@ -30,11 +31,19 @@ class Ex4dRadamSlicedTensor(C.Structure):
                 ("grad", C.c_void_p * 8), ("first_dev", C.c_void_p)]
 
 
+class Ex4dRadamSlicedRegTensor(C.Structure):
+    _fields_ = [("t", Ex4dRadamSlicedTensor), ("reg_kind", C.c_int32), ("reserved", C.c_int32), ("reg_weight", C.c_double), ("reg_rows", C.c_int64)]
+
+
 def _lib():
     lib = _C.load()
     if not getattr(lib, "_optim_ready", False):
         lib.ex4d_radam_step_sliced.restype = C.c_int
         lib.ex4d_radam_step_sliced.argtypes = [C.POINTER(Ex4dRadamSlicedTensor), C.c_int32, C.c_double, C.c_double, C.c_double, C.c_void_p]
+        lib.ex4d_radam_step_sliced_reg.restype = C.c_int
+        lib.ex4d_radam_step_sliced_reg.argtypes = [C.POINTER(Ex4dRadamSlicedRegTensor), C.c_int32, C.c_double, C.c_double, C.c_double, C.c_void_p]
+        lib.ex4d_radam_sliced_reg_rows.restype = C.c_int32
+        lib.ex4d_radam_sliced_reg_rows.argtypes = [C.c_int32, C.c_int32]
         lib.ex4d_optim_last_error.restype = C.c_char_p
         lib.ex4d_radam_step.restype = C.c_int
         lib.ex4d_radam_step.argtypes = [C.POINTER(Ex4dRadamTensor), C.c_int32, C.c_double, C.c_double, C.c_double, C.c_void_p]
@@ -59,13 +68,7 @@ def radam_step_raw(items, betas, eps, device):
                 raise RuntimeError(lib.ex4d_optim_last_error().decode())
 
 
-def radam_step_sliced_raw(items, betas, eps, device):
-    """ex4d_radam_step_sliced over keyframe tensors [rows, K, C] with windowed gradients.  items: iterable of
-    (param_ptr, exp_avg_ptr, exp_avg_sq_ptr, rows, K, C, lr, step, windows[, first_dev_ptr]) with windows = [(first, count, grad_ptr), ...]
-    (<= 8), grad_ptr -> [rows, count, C] floats; first_dev_ptr (optional): device int32 array of the windows' first keyframes, read by
-    the kernel instead of the host values (no device -> host round trip when the positions were gathered from other ranks).
-    Bit-identical to radam_step_raw on the dense gradient the windows add up to."""
-    lib = _lib()
+def _sliced_descs(items):
     descs = []
     for it in items:
         (p, m, v, rows, K, Cc, lr, step, windows), first_dev = it[:9], (it[9] if len(it) > 9 else None)
@@ -78,14 +81,50 @@ def radam_step_sliced_raw(items, betas, eps, device):
         first = (C.c_int32 * 8)(*([(0 if w[0] is None else int(w[0])) for w in windows] + [0] * (8 - len(windows))))
         count = (C.c_int32 * 8)(*([w[1] for w in windows] + [0] * (8 - len(windows))))
         grad = (C.c_void_p * 8)(*([int(w[2]) for w in windows] + [None] * (8 - len(windows))))
-        descs.append(Ex4dRadamSlicedTensor(int(p), int(m), int(v), int(rows), int(K), int(Cc), float(lr), int(step), len(windows), first, count, grad,
-                                           int(first_dev) if first_dev else None))
+        descs.append((Ex4dRadamSlicedTensor(int(p), int(m), int(v), int(rows), int(K), int(Cc), float(lr), int(step), len(windows), first, count, grad,
+                                            int(first_dev) if first_dev else None), it[10:]))
+    return descs
+
+
+def radam_step_sliced_raw(items, betas, eps, device):
+    """ex4d_radam_step_sliced over keyframe tensors [rows, K, C] with windowed gradients.  items: iterable of
+    (param_ptr, exp_avg_ptr, exp_avg_sq_ptr, rows, K, C, lr, step, windows[, first_dev_ptr]) with windows = [(first, count, grad_ptr), ...]
+    (<= 8), grad_ptr -> [rows, count, C] floats; first_dev_ptr (optional): device int32 array of the windows' first keyframes, read by
+    the kernel instead of the host values (no device -> host round trip when the positions were gathered from other ranks).
+    Bit-identical to radam_step_raw on the dense gradient the windows add up to."""
+    lib = _lib()
+    descs = [d for d, _ in _sliced_descs(items)]
     with torch.cuda.device(device):
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         for i in range(0, len(descs), MAX_SLICED):
             chunk = descs[i:i + MAX_SLICED]
             arr = (Ex4dRadamSlicedTensor * len(chunk))(*chunk)
             if lib.ex4d_radam_step_sliced(arr, len(chunk), betas[0], betas[1], eps, stream):
+                raise RuntimeError(lib.ex4d_optim_last_error().decode())
+
+
+def sliced_reg_rows(K, Cc):
+    """Rows of a [rows, K, C] tensor one workgroup of ex4d_radam_step_sliced_reg owns; 0: K is too large for the fused step."""
+    return int(_lib().ex4d_radam_sliced_reg_rows(int(K), int(Cc)))
+
+
+def radam_step_sliced_reg_raw(items, betas, eps, device):
+    """ex4d_radam_step_sliced_reg: radam_step_sliced_raw with a motion regulariser's gradient (train.py:159-168) formed inside the
+    kernel from each Gaussian's own row and added to the windows last.  items: the tuples of radam_step_sliced_raw with first_dev_ptr
+    present (None = host positions) followed by (reg_kind, reg_weight, reg_rows): REG_NONE / REG_MOTION ([rows,K,3]) / REG_ROT
+    ([rows,K,4]), the term's weight of this step and the model's full dynamic count Nd (the mean is over Nd (K-1) terms; `rows` may
+    be a row range).  Bit-identical to radam_step_raw on (windows scattered into zeros + regularizers.backward_raw(accumulate=1))."""
+    lib = _lib()
+    descs = []
+    for d, tail in _sliced_descs(items):
+        kind, weight, reg_rows = tail
+        descs.append(Ex4dRadamSlicedRegTensor(d, int(kind), 0, float(weight), int(reg_rows)))
+    with torch.cuda.device(device):
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        for i in range(0, len(descs), MAX_SLICED):
+            chunk = descs[i:i + MAX_SLICED]
+            arr = (Ex4dRadamSlicedRegTensor * len(chunk))(*chunk)
+            if lib.ex4d_radam_step_sliced_reg(arr, len(chunk), betas[0], betas[1], eps, stream):
                 raise RuntimeError(lib.ex4d_optim_last_error().decode())
 
 

@@ -1,0 +1,139 @@
+"""The motion regularisers of the reference's training loop (train.py:155-168) on the HIP library (include/ex4d_regularizers.h):
+
+    w = regularizer_weights(opt, iteration, gaussians._xyz_motion.shape[0])
+    loss += motion_regularizers(gaussians._xyz_disp, gaussians._xyz_motion, gaussians._rotation_motion, *w)
+
+replaces the three `if opt.*_reg > 0 ...` blocks: one forward launch pair and one backward launch per tensor instead of ~20
+element-wise torch kernels and their autograd graph over the keyframe tensors.  Works with torch.optim.RAdam and FusedRAdam.
+trainer.FrameTrainer(regularizers=...) goes further: with sliced keyframe gradients the two keyframe terms are formed inside the
+optimizer step (optim.radam_step_sliced_reg_raw) and their dense gradient never exists.
+No CPU fallback: everything here needs the HIP library and a ROCm device.
+"""
+import ctypes as C
+
+import torch
+
+from . import _C
+
+EXPORTS = ("ex4d_reg_last_error", "ex4d_reg_scratch_bytes", "ex4d_reg_forward", "ex4d_reg_backward")
+
+
+def _lib():
+    lib = _C.load()
+    if not getattr(lib, "_reg_ready", False):
+        lib.ex4d_reg_last_error.restype = C.c_char_p
+        lib.ex4d_reg_scratch_bytes.restype = C.c_size_t
+        lib.ex4d_reg_scratch_bytes.argtypes = []
+        lib.ex4d_reg_forward.restype = C.c_int
+        lib.ex4d_reg_forward.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_double,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.ex4d_reg_backward.restype = C.c_int
+        lib.ex4d_reg_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                                          C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_int32, C.c_void_p]
+        lib._reg_ready = True
+    return lib
+
+
+def _get(opt, name):
+    return opt[name] if isinstance(opt, dict) else getattr(opt, name)
+
+
+def regularizer_weights(opt, iteration, num_dynamic):
+    """The gates of train.py:156, :159, :163: (static_reg, motion_reg, rot_reg) as they act at `iteration` (0.0 = term off).
+    opt: the reference's OptimizationParams (or a dict of its fields)."""
+    late_static = iteration > _get(opt, "progressive_growing_steps") + _get(opt, "make_dynamic_interval")
+    late_motion = iteration > _get(opt, "progressive_growing_steps") * _get(opt, "extract_every") + _get(opt, "make_dynamic_interval")
+    s, m, r = (float(_get(opt, n)) for n in ("static_reg", "motion_reg", "rot_reg"))
+    return (s if s > 0 and late_static else 0.0,
+            m if m > 0 and late_motion and num_dynamic > 0 else 0.0,
+            r if r > 0 and late_motion and num_dynamic > 0 else 0.0)
+
+
+def _check_inputs(xyz_disp, xyz_motion, rotation_motion):
+    dev = None
+    for t, tail in ((xyz_disp, (3,)), (xyz_motion, None), (rotation_motion, None)):
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise RuntimeError(f"regularizers: tensor on {t.device}: the motion regularisers only run on a ROCm GPU (no CPU fallback)")
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise RuntimeError("regularizers: parameters must be contiguous float32")
+        dev = t.device
+    if dev is None:
+        raise RuntimeError("regularizers: no tensor given")
+    Ns = xyz_disp.shape[0] if xyz_disp is not None else 0
+    if xyz_disp is not None and tuple(xyz_disp.shape[1:]) != (3,):
+        raise RuntimeError("regularizers: _xyz_disp must be [Ns, 3]")
+    Nd, K = 0, 1
+    for t, Cc in ((xyz_motion, 3), (rotation_motion, 4)):
+        if t is None:
+            continue
+        if t.dim() != 3 or t.shape[2] != Cc:
+            raise RuntimeError(f"regularizers: keyframe tensor must be [Nd, K, {Cc}]")
+        if Nd and (t.shape[0], t.shape[1]) != (Nd, K):
+            raise RuntimeError("regularizers: _xyz_motion and _rotation_motion disagree on [Nd, K]")
+        Nd, K = t.shape[0], t.shape[1]
+    return dev, Ns, Nd, K
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None and t.numel() > 0 else None
+
+
+def forward_raw(xyz_disp, xyz_motion, rotation_motion, weights, out=None, scratch=None):
+    """ex4d_reg_forward on the current stream: float32[4] on the device = (static mean, motion mean, rot mean, weighted sum).
+    out / scratch: reusable buffers (scratch: new_scratch(device))."""
+    dev, Ns, Nd, K = _check_inputs(xyz_disp, xyz_motion, rotation_motion)
+    lib = _lib()
+    if out is None:
+        out = torch.empty(4, dtype=torch.float32, device=dev)
+    if scratch is None:
+        scratch = new_scratch(dev)
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        if lib.ex4d_reg_forward(_ptr(xyz_disp), Ns, _ptr(xyz_motion), _ptr(rotation_motion), Nd, K, float(weights[0]), float(weights[1]),
+                                float(weights[2]), out.data_ptr(), scratch.data_ptr(), stream):
+            raise RuntimeError(lib.ex4d_reg_last_error().decode())
+    return out
+
+
+def new_scratch(device):
+    return torch.empty(_lib().ex4d_reg_scratch_bytes() // 8, dtype=torch.float64, device=device)
+
+
+def backward_raw(xyz_disp, xyz_motion, rotation_motion, weights, grads, upstream=None, accumulate=False):
+    """ex4d_reg_backward on the current stream.  grads: (g_xyz_disp, g_xyz_motion, g_rotation_motion), None = skip that tensor;
+    upstream: one-element float32 device tensor multiplied into the gradients (None = 1); accumulate: add instead of write."""
+    dev, Ns, Nd, K = _check_inputs(xyz_disp, xyz_motion, rotation_motion)
+    lib = _lib()
+    for g, p in zip(grads, (xyz_disp, xyz_motion, rotation_motion)):
+        if g is not None and (p is None or g.shape != p.shape or g.dtype != torch.float32 or not g.is_contiguous() or g.device != p.device):
+            raise RuntimeError("regularizers: a gradient must be contiguous float32 of its parameter's shape, on its device")
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        if lib.ex4d_reg_backward(_ptr(xyz_disp), _ptr(grads[0]), Ns, _ptr(xyz_motion), _ptr(grads[1]), _ptr(rotation_motion), _ptr(grads[2]), Nd, K,
+                                 float(weights[0]), float(weights[1]), float(weights[2]), _ptr(upstream), int(bool(accumulate)), stream):
+            raise RuntimeError(lib.ex4d_reg_last_error().decode())
+
+
+class _MotionRegularizers(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, xyz_disp, xyz_motion, rotation_motion, static_reg, motion_reg, rot_reg):
+        ctx.weights = (float(static_reg), float(motion_reg), float(rot_reg))
+        ctx.save_for_backward(xyz_disp, xyz_motion, rotation_motion)
+        return forward_raw(xyz_disp.detach(), xyz_motion.detach(), rotation_motion.detach(), ctx.weights)[3]
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        params = [p.detach() for p in ctx.saved_tensors]
+        grads = [torch.empty_like(p) if need else None for p, need in zip(params, ctx.needs_input_grad[:3])]
+        up = grad_out.detach().to(torch.float32).reshape(1).contiguous()
+        backward_raw(*params, ctx.weights, grads, upstream=up, accumulate=False)
+        return grads[0], grads[1], grads[2], None, None, None
+
+
+def motion_regularizers(xyz_disp, xyz_motion, rotation_motion, static_reg, motion_reg, rot_reg):
+    """static_reg * mean log(|_xyz_disp| + 0.001) + motion_reg * mean |_xyz_motion[:, :1] - _xyz_motion[:, 1:]| + rot_reg * mean(1 - cos of
+    neighbouring _rotation_motion keyframes, norms clamped at 1e-6): the sum train.py:155-168 adds to the loss, as a 0-d tensor with
+    autograd.  Weights as regularizer_weights returns them (0 = term off; an empty dynamic set contributes 0)."""
+    return _MotionRegularizers.apply(xyz_disp, xyz_motion, rotation_motion, static_reg, motion_reg, rot_reg)

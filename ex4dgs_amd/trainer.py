@@ -50,7 +50,7 @@ class FrameTrainer:
     all-gather; implies optimizer).  optimizer: False | True (replicated fused RAdam when exchange != "sharded")."""
 
     def __init__(self, model, exchange="none", optimizer=False, lrs=None, overlap=True, group=None, sliced=None, spatial_lr_scale=1.0,
-                 force_collectives=False, async_forward=None, views_per_step=1):
+                 force_collectives=False, async_forward=None, views_per_step=1, regularizers=None):
         """lrs: overrides of the reference table reference_lrs(spatial_lr_scale).
         sliced (default: on whenever an optimizer runs, replicated or sharded): the keyframe gradients stay [Nd,4,3] / [Nd,2,4] slices from
         the attribute backward through the exchange into ex4d_radam_step_sliced -- no 196 MB zero fill, no dense read.  Replicated
@@ -66,7 +66,13 @@ class FrameTrainer:
         views_per_step = k > 1 (round 6): a rank renders k views per optimizer step; their gradients are added up locally (persistent
         accumulators), exchanged ONCE after the k-th view and applied once -- the batch of a step is N k views, the wire time per view
         1/k of the single-view step's (DESIGN.md section 6 has the projected efficiencies).  Keyframe gradients are dense in this mode (k
-        views touch k windows; the sliced optimizer takes one window per rank), the forward is synchronous."""
+        views touch k windows; the sliced optimizer takes one window per rank), the forward is synchronous.
+        regularizers (default None: off): the weights (static_reg, motion_reg, rot_reg) of the reference's motion regularisers
+        (train.py:155-168) as a 3-tuple, or a callable returning them, asked once per frame -- e.g.
+        lambda: regularizers.regularizer_weights(opt, iteration, Nd).  Their gradients join the frame's in the optimizer step: with sliced
+        keyframe gradients the two keyframe terms are formed inside ex4d_radam_step_sliced_reg from the rows it updates (no dense
+        gradient), _xyz_disp's term is added to its gradient buffer; with dense keyframe gradients all three are added once per optimizer
+        step.  last["reg"]: float32[4] on the device = (static, motion, rot mean, weighted sum) at the frame's parameters."""
         assert exchange in ("none", "allreduce", "sharded")
         self.k = int(views_per_step)
         assert self.k >= 1
@@ -78,6 +84,20 @@ class FrameTrainer:
             sliced, async_forward = False, False
         self._acc, self._nacc = None, 0
         self.model = model
+        self.regularizers = regularizers
+        self._reg_w = self._reg_out = self._reg_scratch = None
+        if regularizers is not None:
+            if exchange != "none":
+                raise NotImplementedError("regularizers on a FrameTrainer need exchange='none': every rank would add the full term to its gradient")
+            if not optimizer:
+                raise ValueError("regularizers join the gradients inside the optimizer step: optimizer=True")
+            if model.num_dynamic > 0 and self.k == 1:
+                from .optim import sliced_reg_rows
+                K = model._xyz_motion.shape[1]
+                if min(sliced_reg_rows(K, 3), sliced_reg_rows(K, 4)) == 0:     # K too large for the fused step's row staging: dense keyframe gradients
+                    if sliced:
+                        raise ValueError(f"regularizers with sliced keyframe gradients: K = {K} keyframes do not fit the fused step (sliced=False works)")
+                    sliced = False
         self.names = list(attr.PARAM_ORDER)
         self.params = [getattr(model, n) for n in self.names]
         self.device = self.params[0].device
@@ -300,7 +320,22 @@ class FrameTrainer:
                 else:                                      # sharded: one reduce-scatter over the dense tensors + the window all-to-all
                     self.opt.launch_exchange(grads, windows)
         self.last = {"radii": radii}
+        self._note_regularizers()
         return out
+
+    def _note_regularizers(self):
+        """The frame's regulariser weights and loss terms (at the parameters the frame was rendered with), on the main stream."""
+        if self.regularizers is None:
+            return
+        from . import regularizers as reg
+        w = self.regularizers() if callable(self.regularizers) else self.regularizers
+        self._reg_w = tuple(float(x) for x in w)
+        assert len(self._reg_w) == 3
+        if self._reg_out is None:
+            self._reg_out = torch.empty(4, dtype=torch.float32, device=self.device)
+            self._reg_scratch = reg.new_scratch(self.device)
+        m = self.model
+        self.last["reg"] = reg.forward_raw(m._xyz_disp, m._xyz_motion, m._rotation_motion, self._reg_w, out=self._reg_out, scratch=self._reg_scratch)
 
     def _apply_optimizer(self):
         if self.async_forward:
@@ -311,8 +346,17 @@ class FrameTrainer:
         if self.mode == "sharded":
             self.opt.step()                                # (its exchange was launched by _run_frame: launch_exchange(grads, windows))
         else:
-            from .optim import radam_step_raw, radam_step_sliced_raw
+            from .optim import radam_step_raw, radam_step_sliced_raw, radam_step_sliced_reg_raw, REG_MOTION, REG_ROT
             self.steps += 1
+            w = self._reg_w if self.regularizers is not None and self._reg_w is not None and any(self._reg_w) else None
+            if w is not None:
+                # dense gradients take their terms here (added to the frame's gradient buffers); sliced keyframe tensors in the step below
+                from . import regularizers as reg
+                gi = [self._grads[self.names.index(n)] for n in ("_xyz_disp", "_xyz_motion", "_rotation_motion")]
+                if self.sliced:
+                    gi[1] = gi[2] = None
+                m_ = self.model
+                reg.backward_raw(m_._xyz_disp, m_._xyz_motion, m_._rotation_motion, w, gi, accumulate=True)
             items = [(p.data_ptr(), g.data_ptr(), mm.data_ptr(), vv.data_ptr(), p.numel(), lr, self.steps, int(self.names[i] in NAN_TO_NUM))
                      for i, (p, g, mm, vv, lr) in enumerate(zip(self.params, self._grads, self.m, self.v, self.lrs)) if i not in self.kf_idx]
             radam_step_raw(items, (0.9, 0.999), 1e-8, self.device)
@@ -323,7 +367,13 @@ class FrameTrainer:
                     count, Cc = attr.SLICED_SHAPES[self.names[i]]
                     sl.append((p.data_ptr(), self.m[i].data_ptr(), self.v[i].data_ptr(), p.shape[0], p.shape[1], Cc, self.lrs[i], self.steps,
                                gth.windows(count), gth.first_device_ptr()))
-                radam_step_sliced_raw(sl, (0.9, 0.999), 1e-8, self.device)
+                    if w is not None:
+                        motion = self.names[i] == "_xyz_motion"
+                        sl[-1] += (REG_MOTION if motion else REG_ROT, w[1] if motion else w[2], p.shape[0])
+                if w is not None:
+                    radam_step_sliced_reg_raw(sl, (0.9, 0.999), 1e-8, self.device)
+                else:
+                    radam_step_sliced_raw(sl, (0.9, 0.999), 1e-8, self.device)
             torch.autograd.graph.increment_version(self.params)
         self._grads = None
 

@@ -69,6 +69,27 @@ typedef struct Ex4dRadamSlicedTensor {
 
 int ex4d_radam_step_sliced(const Ex4dRadamSlicedTensor *tensors, int32_t count, double beta1, double beta2, double eps, void *stream);
 
+/* ex4d_radam_step_sliced with a motion regulariser of the reference (train.py:159-168, ex4d_regularizers.h) added to the gradient:
+ *     gradient = windows (summed in index order) + regulariser gradient (added last)
+ * reg_kind 0: none (the bits of ex4d_radam_step_sliced); 1: motion_reg on a [rows,K,3] tensor; 2: rot_reg on a [rows,K,4] tensor.
+ * The regulariser gradient of a keyframe is a function of its Gaussian's own row BEFORE the update, so each workgroup owns whole rows,
+ * stages them in LDS and forms the gradient there: the dense gradient never exists in memory, the traffic stays 24 B per element plus
+ * the windows.  Its coefficient is reg_weight / (reg_rows (K-1)), on the host in double, cast to float32; reg_rows is the model's full
+ * dynamic count (`rows` may be a row range of it).  K = 1 or reg_weight = 0: no term, a plain sliced step.
+ * Bit-identical to ex4d_radam_step on (windows scattered into zeros, then ex4d_reg_backward with accumulate = 1).
+ * A K so large that four rows do not fit the staging LDS returns EX4D_ERR_ARG (ex4d_radam_sliced_reg_rows gives 0): take the dense path. */
+typedef struct Ex4dRadamSlicedRegTensor {
+    Ex4dRadamSlicedTensor t;
+    int32_t reg_kind;
+    int32_t reserved;
+    double reg_weight;       /* motion_reg or rot_reg of this step (0 = off) */
+    int64_t reg_rows;        /* Nd of the mean's 1 / (Nd (K-1)); >= t.rows */
+} Ex4dRadamSlicedRegTensor;
+
+int ex4d_radam_step_sliced_reg(const Ex4dRadamSlicedRegTensor *tensors, int32_t count, double beta1, double beta2, double eps, void *stream);
+/* rows one workgroup of ex4d_radam_step_sliced_reg owns for a [rows,K,C] tensor (a multiple of 4, at most 32); 0: K too large */
+int32_t ex4d_radam_sliced_reg_rows(int32_t K, int32_t C);
+
 #ifdef __cplusplus
 }
 #endif

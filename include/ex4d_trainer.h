@@ -13,9 +13,10 @@
  * a frame needs more), so the only host <-> device synchronisation of an iteration is the instance-count read-back the reference has
  * too (rasterizer_impl.cu:298-299), which overlaps the depth sort.
  *
- * SCOPE: this is the render + L1/SSIM + RAdam core of the iteration, not the reference's whole loop.  Not included (they live in the
- * reference's Python policy layer, out of SURVEY.md 8's scope): the regularisers static_reg / motion_reg / rot_reg (train.py:156-168;
- * motion_reg and rot_reg make the keyframe gradients dense over all K, which the sliced optimizer path here does not take), the
+ * SCOPE: this is the render + L1/SSIM + regularisers + RAdam core of the iteration, not the reference's whole loop.  The regularisers
+ * static_reg / motion_reg / rot_reg (train.py:156-168) are off until ex4d_trainer_set_regularizers gives them weights; the keyframe
+ * terms, dense over all K, are formed inside ex4d_radam_step_sliced_reg, so the keyframe gradients stay slices.  Not included (they
+ * live in the reference's Python policy layer, out of SURVEY.md 8's scope): the
  * l1_accum error-map hook on the flow output (train.py:149-152: dL_dout_flow is NULL here, so viewspace_l1points stays zero),
  * densification / pruning and their statistics.  What the loop changes over time is settable: ex4d_trainer_set_lr (the position
  * learning-rate schedule, update_learning_rate) and ex4d_trainer_set_sh_degree (oneupSHdegree every 1000 iterations).
@@ -81,17 +82,23 @@ int ex4d_trainer_set_sh_degree(Ex4dTrainer *t, int32_t degree);
  * again before anything is applied: same parameters as the synchronous path.  ex4d_trainer_replays counts such re-runs. */
 int ex4d_trainer_set_async(Ex4dTrainer *t, int32_t on);
 int64_t ex4d_trainer_replays(const Ex4dTrainer *t);
+/* Weights of the motion regularisers (ex4d_regularizers.h) from the next step on, as they act at that iteration -- the iteration gates
+ * of train.py:156-163 are the caller's (regularizers.regularizer_weights).  All 0 (the default) = off: the sequence above, unchanged.
+ * On: ex4d_reg_forward fills output 6, _xyz_disp's term is added to its gradient, the keyframe terms go through
+ * ex4d_radam_step_sliced_reg.  Needs optimizer = 1; EX4D_ERR_ARG when K is too large for that step. */
+int ex4d_trainer_set_regularizers(Ex4dTrainer *t, double static_reg, double motion_reg, double rot_reg);
 
 /* Device pointers into the trainer's workspace, valid until the next step / destroy:
  * what = 0 loss [1], 1 render [3,H,W], 2 radii int32 [P], 3 dL_dmeans2D [P,3] (viewspace gradient, densification statistics),
- *        4 depth [1,H,W], 5 acc [1,H,W]. */
+ *        4 depth [1,H,W], 5 acc [1,H,W], 6 regularisers float[4] = {static mean, motion mean, rot mean, weighted sum} of the last step
+ *        that had them on (zeros before); the loss of what = 0 stays the L1/SSIM loss. */
 const void *ex4d_trainer_output(const Ex4dTrainer *t, int32_t what);
 /* Gradient of parameter i of the last step: dense [shape of the parameter] except i = 7 (_xyz_motion: [Nd,4,3]) and i = 8
  * (_rotation_motion: [Nd,2,4]), the slices of ex4d_attributes_backward_sliced; slices4 (host int32[4], may be NULL) receives
  * {xyz first, 4, rotation first, 2}. */
 const float *ex4d_trainer_grad(const Ex4dTrainer *t, int32_t i, int32_t *slices4);
 /* Asynchronous device-to-device copy of one of the buffers above into caller memory (bindings that cannot wrap a raw pointer):
- * what = 0..5 as in ex4d_trainer_output, 100 + i = gradient of parameter i.  `bytes` must not exceed the buffer's size. */
+ * what = 0..6 as in ex4d_trainer_output, 100 + i = gradient of parameter i.  `bytes` must not exceed the buffer's size. */
 int ex4d_trainer_read(const Ex4dTrainer *t, int32_t what, void *dst, size_t bytes, void *stream);
 /* bytes of device memory the trainer holds (workspace + optimizer state + arenas) */
 size_t ex4d_trainer_bytes(const Ex4dTrainer *t);
