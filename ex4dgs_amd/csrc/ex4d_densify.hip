@@ -59,11 +59,9 @@ __global__ __launch_bounds__(DN_THREADS) void densify_stats_kernel(float *__rest
 // ---------------------------------------------------------------------------------------------------------------- plan
 __device__ __forceinline__ float max3(float a, float b, float c)
 {
-    // torch.max(dim=1).values propagates NaN
-    float m = a;
-    if (!(b <= m)) m = b;
-    if (!(c <= m)) m = c;
-    return m;
+    // torch.max(dim=1).values propagates NaN, whichever column holds it
+    const float m = (a != a || a >= b) ? a : b;
+    return (m != m || m >= c) ? m : c;
 }
 
 struct PlanArgs {

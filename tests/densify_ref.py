@@ -2,7 +2,8 @@
 train.py:199-216), with explicit random draws: the checker of ex4dgs_amd.densify, pinned itself by tests/golden/densify.npz.
 
 State: {"params": {name: tensor}, "m": {name: tensor} | None, "v": ..., "stats": {reference stat name: tensor}} with the
-reference's shapes ([N, 1] statistics, [N] radii).  Draws: the keys of ex4dgs_amd.densify._draws.
+reference's shapes ([N, 1] statistics, [N] radii); new tensors are allocated in the inputs' dtype, so a float64 state gives the float64
+restatement.  Draws: the keys of ex4dgs_amd.densify._draws.
 """
 import torch
 
@@ -16,12 +17,12 @@ D_STATS = ("motion_xyz_gradient_accum", "motion_denom", "motion_xyz_error_mean",
 INIT = (0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1000.0, 1000.0, -1.0)
 
 
-def init_stats(ns, nd, device="cpu"):
+def init_stats(ns, nd, device="cpu", dtype=torch.float32):
     out = {}
     for names, n in ((S_STATS, ns), (D_STATS, nd)):
         for k, v in zip(names, INIT):
             shape = (n,) if k.endswith("radii2D") else (n, 1)
-            out[k] = torch.full(shape, v, dtype=torch.float32, device=device)
+            out[k] = torch.full(shape, v, dtype=dtype, device=device)
     return out
 
 
@@ -50,13 +51,13 @@ def update(st, radii, vgrad, egrad, timestamp, densify_stats=True, prune_stats=T
             st[names[7]][vis] = torch.where(hit, l1, st[names[7]][vis])
             st[names[2]][vis] += l1
             st[names[3]][vis] += e[vis, 2:3] / e[vis, 0:1].clamp_min(1e-4)
-            st[names[4]][vis] += (e[vis, 0:1] > 0).float()
+            st[names[4]][vis] += (e[vis, 0:1] > 0).to(e.dtype)
 
 
 def _rot(r):
     norm = torch.sqrt(r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1] + r[:, 2] * r[:, 2] + r[:, 3] * r[:, 3])
     q = r / norm[:, None]
-    R = torch.zeros((q.size(0), 3, 3), device=r.device)
+    R = torch.zeros((q.size(0), 3, 3), dtype=r.dtype, device=r.device)
     r, x, y, z = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
     R[:, 0, 0] = 1 - 2 * (y * y + z * z); R[:, 0, 1] = 2 * (x * y - r * z); R[:, 0, 2] = 2 * (x * z + r * y)
     R[:, 1, 0] = 2 * (x * y + r * z); R[:, 1, 1] = 1 - 2 * (x * x + z * z); R[:, 1, 2] = 2 * (y * z - r * x)
@@ -82,7 +83,7 @@ def _cat(state, names, stat_names, new, n_new):
                 state[mk][k] = torch.cat([state[mk][k], torch.zeros_like(new[k])])
     n = P[names[0]].shape[0]
     for k, v in zip(stat_names[:7], INIT[:7]):
-        st[k] = torch.full((n,) if k.endswith("radii2D") else (n, 1), v, device=P[names[0]].device)
+        st[k] = torch.full((n,) if k.endswith("radii2D") else (n, 1), v, dtype=P[names[0]].dtype, device=P[names[0]].device)
 
 
 def _gather(state, names, stat_names, keep):
@@ -123,7 +124,7 @@ def densify_and_prune(state, model, max_grad, max_dgrad, min_opacity, min_motion
     # ---- split (:874), N = 2, over the post-clone set
     N = 2
     n0 = P["_xyz"].shape[0]
-    pad = torch.zeros(n0, device=P["_xyz"].device)
+    pad = torch.zeros(n0, dtype=P["_xyz"].dtype, device=P["_xyz"].device)
     pad[:grads["s"].shape[0]] = grads["s"].squeeze(-1)
     sc = torch.exp(P["_scaling"])
     ss = (pad >= max_grad) & (sc.max(dim=1).values > percent_dense * extent)
@@ -135,12 +136,12 @@ def densify_and_prune(state, model, max_grad, max_dgrad, min_opacity, min_motion
     new["_scaling"] = torch.log(sc[ss].repeat(N, 1) / (0.8 * N))
     prune_s = torch.cat([ss, torch.zeros(N * int(ss.sum()), dtype=torch.bool, device=ss.device)])
     m = int(ss.sum()) * N
-    st["xyz_error_min"] = torch.cat([st["xyz_error_min"], torch.full((m, 1), 1000.0, device=ss.device)])
-    st["xyz_error_min_timestamp"] = torch.cat([st["xyz_error_min_timestamp"], torch.full((m, 1), -1.0, device=ss.device)])
+    st["xyz_error_min"] = torch.cat([st["xyz_error_min"], torch.full((m, 1), 1000.0, dtype=pad.dtype, device=ss.device)])
+    st["xyz_error_min_timestamp"] = torch.cat([st["xyz_error_min_timestamp"], torch.full((m, 1), -1.0, dtype=pad.dtype, device=ss.device)])
     if has_d:
         n1 = P["_xyz_motion"].shape[0]
         K = P["_xyz_motion"].shape[1]
-        padd = torch.zeros(n1, device=pad.device)
+        padd = torch.zeros(n1, dtype=pad.dtype, device=pad.device)
         padd[:grads["d"].shape[0]] = grads["d"].squeeze(-1)
         scd = torch.exp(P["_scaling_motion"])
         sd = (padd >= max_dgrad) & (scd.max(dim=1).values > percent_dense * extent)
@@ -155,8 +156,8 @@ def densify_and_prune(state, model, max_grad, max_dgrad, min_opacity, min_motion
         newd["_opacity_duration_var"] = torch.ones_like(newd["_opacity_duration_var"]) * 2
         prune_d = torch.cat([sd, torch.zeros(N * int(sd.sum()), dtype=torch.bool, device=sd.device)])
         md = int(sd.sum()) * N
-        st["motion_xyz_error_min"] = torch.cat([st["motion_xyz_error_min"], torch.full((md, 1), 1000.0, device=sd.device)])
-        st["motion_xyz_error_min_timestamp"] = torch.cat([st["motion_xyz_error_min_timestamp"], torch.full((md, 1), -1.0, device=sd.device)])
+        st["motion_xyz_error_min"] = torch.cat([st["motion_xyz_error_min"], torch.full((md, 1), 1000.0, dtype=pad.dtype, device=sd.device)])
+        st["motion_xyz_error_min_timestamp"] = torch.cat([st["motion_xyz_error_min_timestamp"], torch.full((md, 1), -1.0, dtype=pad.dtype, device=sd.device)])
         _cat(state, DYNAMIC, D_STATS, newd, None)
     _cat(state, STATIC, S_STATS, new, None)
     # ---- prune (:1034-1070): split originals + opacity + screen terms + the l1 / ssim masks on the reset statistics
