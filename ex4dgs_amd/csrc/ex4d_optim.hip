@@ -260,7 +260,7 @@ __global__ __launch_bounds__(256) void radam_sliced_reg_kernel(const RegArgs a)
 
 thread_local char g_optim_err[256] = "";
 
-static bool fill_coefficients(RadamSlot &s, double lr, long long step, double beta1, double beta2, double eps)
+static void fill_coefficients(RadamSlot &s, double lr, long long step, double beta1, double beta2, double eps)
 {
     // the Python-double scalar arithmetic of torch's RAdam, cast to float32 where it meets a tensor
     const double rho_inf = 2.0 / (1.0 - beta2) - 1.0;
@@ -271,7 +271,56 @@ static bool fill_coefficients(RadamSlot &s, double lr, long long step, double be
     s.bc1 = (float)bc1; s.lr = (float)lr; s.sqrt_bc2 = (float)std::sqrt(bc2); s.eps = (float)eps;
     s.rectified = rho_t > 5.0;
     s.rect = s.rectified ? (float)std::sqrt((rho_t - 4.0) * (rho_t - 2.0) * rho_inf / ((rho_inf - 4.0) * (rho_inf - 2.0) * rho_t)) : 0.f;
+}
+
+// ---- what the three entry points share.  The bool helpers leave the fault's text in g_optim_err and return false.
+static bool count_fits(int32_t count, int max, const void *tensors)
+{
+    if (count >= 0 && count <= max && (count == 0 || tensors)) return true;
+    snprintf(g_optim_err, sizeof(g_optim_err), "count %d outside [0, %d]", count, max);
+    return false;
+}
+
+// validates descriptor i and fills its slot, all but first_block: how many workgroups a tensor takes is the entry point's business
+static bool fill_sliced(SlicedSlot &s, const Ex4dRadamSlicedTensor &t, int i, double beta1, double beta2, double eps)
+{
+    if (t.rows < 0 || t.K < 1 || (t.C != 3 && t.C != 4) || t.step < 1 || !t.param || !t.exp_avg || !t.exp_avg_sq ||
+        t.n_windows < 0 || t.n_windows > EX4D_RADAM_MAX_WINDOWS) {
+        snprintf(g_optim_err, sizeof(g_optim_err), "sliced tensor %d: bad shape, step < 1, null pointer or too many windows", i);
+        return false;
+    }
+    s.s.p = t.param; s.s.g = nullptr; s.s.m = t.exp_avg; s.s.v = t.exp_avg_sq; s.s.numel = t.rows * t.K * t.C; s.s.first_chunk = 0; s.s.sanitize = 0;
+    s.first_dev = t.first_dev;
+    fill_coefficients(s.s, t.lr, t.step, beta1, beta2, eps);
+    s.slices = t.rows * t.K; s.K = t.K; s.C = t.C; s.nw = t.n_windows;
+    for (int w = 0; w < EX4D_RADAM_MAX_WINDOWS; w++) {
+        const bool live = w < t.n_windows;
+        if (live && (((t.first[w] < 0 || t.first[w] + t.count[w] > t.K) && !t.first_dev) || t.count[w] < 1 || t.count[w] > t.K || !t.grad[w])) {
+            snprintf(g_optim_err, sizeof(g_optim_err), "sliced tensor %d: window %d outside [0, K) or null", i, w);
+            return false;
+        }
+        s.first[w] = live ? t.first[w] : 0; s.count[w] = live ? t.count[w] : 0; s.grad[w] = live ? t.grad[w] : nullptr;
+    }
     return true;
+}
+
+// appends a tensor's nb workgroups to the launch: `first` = the index of its first one
+static bool append_blocks(unsigned &blocks, unsigned &first, long long nb)
+{
+    first = blocks;
+    if (nb + blocks > 0x7fffffffLL) { snprintf(g_optim_err, sizeof(g_optim_err), "too many elements for one launch"); return false; }
+    blocks += (unsigned)nb;
+    return true;
+}
+
+template <class Args>
+static int launch(void (*kernel)(Args), unsigned blocks, size_t lds, void *stream, const Args &a)
+{
+    if (blocks == 0) return EX4D_OK;
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), lds, (hipStream_t)stream, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { snprintf(g_optim_err, sizeof(g_optim_err), "launch failed: %s", hipGetErrorString(e)); return EX4D_ERR_HIP; }
+    return EX4D_OK;
 }
 
 }  // namespace
@@ -283,10 +332,7 @@ const char *ex4d_optim_last_error(void) { return g_optim_err; }
 int ex4d_radam_step(const Ex4dRadamTensor *tensors, int32_t count, double beta1, double beta2, double eps, void *stream_)
 {
     g_optim_err[0] = 0;
-    if (count < 0 || count > EX4D_RADAM_MAX_TENSORS || (count > 0 && !tensors)) {
-        snprintf(g_optim_err, sizeof(g_optim_err), "count %d outside [0, %d]", count, EX4D_RADAM_MAX_TENSORS);
-        return EX4D_ERR_ARG;
-    }
+    if (!count_fits(count, EX4D_RADAM_MAX_TENSORS, tensors)) return EX4D_ERR_ARG;
     RadamArgs a;
     a.count = 0;
     unsigned chunks = 0;
@@ -300,59 +346,26 @@ int ex4d_radam_step(const Ex4dRadamTensor *tensors, int32_t count, double beta1,
         RadamSlot &s = a.slot[a.count++];
         s.p = t.param; s.g = t.grad; s.m = t.exp_avg; s.v = t.exp_avg_sq; s.numel = t.numel; s.sanitize = t.nan_to_num != 0;
         fill_coefficients(s, t.lr, t.step, beta1, beta2, eps);
-        s.first_chunk = chunks;
-        const long long c = (t.numel + RADAM_CHUNK - 1) / RADAM_CHUNK;
-        if (c + chunks > 0x7fffffffLL) { snprintf(g_optim_err, sizeof(g_optim_err), "too many elements for one launch"); return EX4D_ERR_ARG; }
-        chunks += (unsigned)c;
+        if (!append_blocks(chunks, s.first_chunk, (t.numel + RADAM_CHUNK - 1) / RADAM_CHUNK)) return EX4D_ERR_ARG;
     }
-    if (chunks == 0) return EX4D_OK;
-    hipLaunchKernelGGL(radam_kernel, dim3(chunks), dim3(256), 0, (hipStream_t)stream_, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { snprintf(g_optim_err, sizeof(g_optim_err), "launch failed: %s", hipGetErrorString(e)); return EX4D_ERR_HIP; }
-    return EX4D_OK;
+    return launch(radam_kernel, chunks, 0, stream_, a);
 }
 
 int ex4d_radam_step_sliced(const Ex4dRadamSlicedTensor *tensors, int32_t count, double beta1, double beta2, double eps, void *stream_)
 {
     g_optim_err[0] = 0;
-    if (count < 0 || count > EX4D_RADAM_MAX_SLICED || (count > 0 && !tensors)) {
-        snprintf(g_optim_err, sizeof(g_optim_err), "count %d outside [0, %d]", count, EX4D_RADAM_MAX_SLICED);
-        return EX4D_ERR_ARG;
-    }
+    if (!count_fits(count, EX4D_RADAM_MAX_SLICED, tensors)) return EX4D_ERR_ARG;
     SlicedArgs a;
     a.count = 0;
     unsigned blocks = 0;
     for (int i = 0; i < count; i++) {
-        const Ex4dRadamSlicedTensor &t = tensors[i];
-        if (t.rows == 0) continue;
-        if (t.rows < 0 || t.K < 1 || (t.C != 3 && t.C != 4) || t.step < 1 || !t.param || !t.exp_avg || !t.exp_avg_sq ||
-            t.n_windows < 0 || t.n_windows > EX4D_RADAM_MAX_WINDOWS) {
-            snprintf(g_optim_err, sizeof(g_optim_err), "sliced tensor %d: bad shape, step < 1, null pointer or too many windows", i);
-            return EX4D_ERR_ARG;
-        }
-        SlicedSlot &s = a.slot[a.count++];
-        s.s.p = t.param; s.s.g = nullptr; s.s.m = t.exp_avg; s.s.v = t.exp_avg_sq; s.s.numel = t.rows * t.K * t.C; s.s.first_chunk = 0; s.s.sanitize = 0;
-        s.first_dev = t.first_dev;
-        fill_coefficients(s.s, t.lr, t.step, beta1, beta2, eps);
-        s.slices = t.rows * t.K; s.K = t.K; s.C = t.C; s.nw = t.n_windows;
-        for (int w = 0; w < EX4D_RADAM_MAX_WINDOWS; w++) {
-            const bool live = w < t.n_windows;
-            if (live && (((t.first[w] < 0 || t.first[w] + t.count[w] > t.K) && !t.first_dev) || t.count[w] < 1 || t.count[w] > t.K || !t.grad[w])) {
-                snprintf(g_optim_err, sizeof(g_optim_err), "sliced tensor %d: window %d outside [0, K) or null", i, w);
-                return EX4D_ERR_ARG;
-            }
-            s.first[w] = live ? t.first[w] : 0; s.count[w] = live ? t.count[w] : 0; s.grad[w] = live ? t.grad[w] : nullptr;
-        }
-        s.first_block = blocks;
-        const long long nb = (s.s.numel + RADAM_CHUNK - 1) / RADAM_CHUNK;
-        if (nb + blocks > 0x7fffffffLL) { snprintf(g_optim_err, sizeof(g_optim_err), "too many elements for one launch"); return EX4D_ERR_ARG; }
-        blocks += (unsigned)nb;
+        if (tensors[i].rows == 0) continue;
+        SlicedSlot &s = a.slot[a.count];
+        if (!fill_sliced(s, tensors[i], i, beta1, beta2, eps) ||
+            !append_blocks(blocks, s.first_block, (s.s.numel + RADAM_CHUNK - 1) / RADAM_CHUNK)) return EX4D_ERR_ARG;
+        a.count++;
     }
-    if (blocks == 0) return EX4D_OK;
-    hipLaunchKernelGGL(radam_sliced_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { snprintf(g_optim_err, sizeof(g_optim_err), "launch failed: %s", hipGetErrorString(e)); return EX4D_ERR_HIP; }
-    return EX4D_OK;
+    return launch(radam_sliced_kernel, blocks, 0, stream_, a);
 }
 
 int32_t ex4d_radam_sliced_reg_rows(int32_t K, int32_t C)
@@ -364,10 +377,7 @@ int32_t ex4d_radam_sliced_reg_rows(int32_t K, int32_t C)
 int ex4d_radam_step_sliced_reg(const Ex4dRadamSlicedRegTensor *tensors, int32_t count, double beta1, double beta2, double eps, void *stream_)
 {
     g_optim_err[0] = 0;
-    if (count < 0 || count > EX4D_RADAM_MAX_SLICED || (count > 0 && !tensors)) {
-        snprintf(g_optim_err, sizeof(g_optim_err), "count %d outside [0, %d]", count, EX4D_RADAM_MAX_SLICED);
-        return EX4D_ERR_ARG;
-    }
+    if (!count_fits(count, EX4D_RADAM_MAX_SLICED, tensors)) return EX4D_ERR_ARG;
     RegArgs a;
     a.count = 0;
     unsigned blocks = 0;
@@ -376,54 +386,30 @@ int ex4d_radam_step_sliced_reg(const Ex4dRadamSlicedRegTensor *tensors, int32_t 
         const Ex4dRadamSlicedTensor &t = tensors[i].t;
         const int kind = tensors[i].reg_kind;
         if (t.rows == 0) continue;
-        if (t.rows < 0 || t.K < 1 || (t.C != 3 && t.C != 4) || t.step < 1 || !t.param || !t.exp_avg || !t.exp_avg_sq ||
-            t.n_windows < 0 || t.n_windows > EX4D_RADAM_MAX_WINDOWS) {
-            snprintf(g_optim_err, sizeof(g_optim_err), "sliced tensor %d: bad shape, step < 1, null pointer or too many windows", i);
-            return EX4D_ERR_ARG;
-        }
+        RegSlot &r = a.slot[a.count];
+        if (!fill_sliced(r.t, t, i, beta1, beta2, eps)) return EX4D_ERR_ARG;
         if (kind < 0 || kind > 2 || (kind == ex4d_reg::KIND_MOTION && t.C != 3) || (kind == ex4d_reg::KIND_ROT && t.C != 4) ||
             (kind != 0 && tensors[i].reg_rows < t.rows)) {
             snprintf(g_optim_err, sizeof(g_optim_err), "sliced tensor %d: reg_kind %d does not fit C = %d, or reg_rows < rows", i, kind, t.C);
             return EX4D_ERR_ARG;
         }
-        RegSlot &r = a.slot[a.count];
         r.R = reg_block_rows(t.K, t.C);
         if (r.R < 4) {
             snprintf(g_optim_err, sizeof(g_optim_err), "sliced tensor %d: four rows of K = %d keyframes do not fit the %d bytes of LDS a workgroup stages "
                      "(dense gradients + ex4d_reg_backward + ex4d_radam_step take any K)", i, t.K, REG_LDS_BYTES);
             return EX4D_ERR_ARG;
         }
-        a.count++;
-        SlicedSlot &s = r.t;
-        s.s.p = t.param; s.s.g = nullptr; s.s.m = t.exp_avg; s.s.v = t.exp_avg_sq; s.s.numel = t.rows * t.K * t.C; s.s.first_chunk = 0; s.s.sanitize = 0;
-        s.first_dev = t.first_dev;
-        fill_coefficients(s.s, t.lr, t.step, beta1, beta2, eps);
-        s.slices = t.rows * t.K; s.K = t.K; s.C = t.C; s.nw = t.n_windows;
-        for (int w = 0; w < EX4D_RADAM_MAX_WINDOWS; w++) {
-            const bool live = w < t.n_windows;
-            if (live && (((t.first[w] < 0 || t.first[w] + t.count[w] > t.K) && !t.first_dev) || t.count[w] < 1 || t.count[w] > t.K || !t.grad[w])) {
-                snprintf(g_optim_err, sizeof(g_optim_err), "sliced tensor %d: window %d outside [0, K) or null", i, w);
-                return EX4D_ERR_ARG;
-            }
-            s.first[w] = live ? t.first[w] : 0; s.count[w] = live ? t.count[w] : 0; s.grad[w] = live ? t.grad[w] : nullptr;
-        }
         // the mean's constant on the host in double; a term with nothing to average (K = 1) or weight 0 is a plain sliced step
         const double pairs = (double)tensors[i].reg_rows * (t.K - 1);
         r.coef = (kind != 0 && pairs > 0) ? (float)(tensors[i].reg_weight / pairs) : 0.f;
         r.kind = r.coef != 0.f ? kind : ex4d_reg::KIND_NONE;
         r.rows = t.rows;
-        s.first_block = blocks;
-        const long long nb = (t.rows + r.R - 1) / r.R;
-        if (nb + blocks > 0x7fffffffLL) { snprintf(g_optim_err, sizeof(g_optim_err), "too many elements for one launch"); return EX4D_ERR_ARG; }
-        blocks += (unsigned)nb;
+        if (!append_blocks(blocks, r.t.first_block, (t.rows + r.R - 1) / r.R)) return EX4D_ERR_ARG;
         const size_t need = 2 * (size_t)r.R * t.K * t.C * sizeof(float);
         lds = need > lds ? need : lds;
+        a.count++;
     }
-    if (blocks == 0) return EX4D_OK;
-    hipLaunchKernelGGL(radam_sliced_reg_kernel, dim3(blocks), dim3(256), lds, (hipStream_t)stream_, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { snprintf(g_optim_err, sizeof(g_optim_err), "launch failed: %s", hipGetErrorString(e)); return EX4D_ERR_HIP; }
-    return EX4D_OK;
+    return launch(radam_sliced_reg_kernel, blocks, lds, stream_, a);
 }
 
 }  // extern "C"

@@ -17,6 +17,11 @@
 
 namespace {
 
+// positions in the parameter order of EX4D_TRAINER_PARAMS (include/ex4d_trainer.h)
+enum { XYZ, XYZ_DISP, ROTATION, OPACITY, SCALING, FEATURES_DC, FEATURES_REST, XYZ_MOTION, ROTATION_MOTION, OPACITY_MOTION,
+       OPACITY_DURATION_CENTER, OPACITY_DURATION_VAR, SCALING_MOTION, FEATURES_DC_MOTION, FEATURES_REST_MOTION };
+static_assert(FEATURES_REST_MOTION + 1 == EX4D_TRAINER_PARAMS, "one name per parameter");
+
 thread_local char t_err[512] = "";
 
 int tfail(int code, const char *fmt, ...)
@@ -137,7 +142,7 @@ Ex4dTrainer *ex4d_trainer_create(const Ex4dTrainerConfig *cfg, float *const *par
     for (int i = 0; i < EX4D_TRAINER_PARAMS && ok; i++) {
         t->param[i] = params[i];
         t->numel[i] = n[i];
-        t->grad_numel[i] = i == 7 ? Nd * 4 * 3 : (i == 8 ? Nd * 2 * 4 : n[i]);
+        t->grad_numel[i] = i == XYZ_MOTION ? Nd * 4 * 3 : (i == ROTATION_MOTION ? Nd * 2 * 4 : n[i]);
         if (n[i] > 0 && !params[i]) { tfail(1, "parameter %d is NULL but has %lld elements", i, (long long)n[i]); ok = false; break; }
         ok = ok && t->take(t->grad[i], (size_t)t->grad_numel[i]);
         if (cfg->optimizer) ok = ok && t->take(t->m[i], (size_t)n[i], true) && t->take(t->v[i], (size_t)n[i], true);
@@ -215,9 +220,10 @@ int ex4d_trainer_step(Ex4dTrainer *t, double timestamp, const float *viewmatrix,
     prm.kernel_size = c.kernel_size; prm.scale_modifier = 1.0f; prm.min_depth = c.min_depth; prm.max_depth = c.max_depth;
     prm.prefiltered = 0; prm.debug = 0; prm.prepare_backward = 1; prm.instance_capacity = 0; prm.assume_no_flow = 0; prm.reserved = 0;
     Ex4dSplitSH sh;
-    sh.dc[0] = p[5]; sh.rest[0] = p[6]; sh.dc[1] = p[13]; sh.rest[1] = p[14]; sh.n_static = c.Ns;
+    sh.dc[0] = p[FEATURES_DC]; sh.rest[0] = p[FEATURES_REST]; sh.dc[1] = p[FEATURES_DC_MOTION]; sh.rest[1] = p[FEATURES_REST_MOTION]; sh.n_static = c.Ns;
     Ex4dSplitSHGrad gsh;
-    gsh.dc[0] = t->grad[5]; gsh.rest[0] = t->grad[6]; gsh.dc[1] = t->grad[13]; gsh.rest[1] = t->grad[14]; gsh.n_static = c.Ns;
+    gsh.dc[0] = t->grad[FEATURES_DC]; gsh.rest[0] = t->grad[FEATURES_REST]; gsh.dc[1] = t->grad[FEATURES_DC_MOTION]; gsh.rest[1] = t->grad[FEATURES_REST_MOTION];
+    gsh.n_static = c.Ns;
     float *const *g = t->grad;
     // Asynchronous mode: the forward does not wait for the instance count (the reference's one host synchronisation per frame,
     // rasterizer_impl.cu:298-299); the frame's status is looked at once, right before the optimizer step -- by then every kernel of the
@@ -273,10 +279,10 @@ int ex4d_trainer_step(Ex4dTrainer *t, double timestamp, const float *viewmatrix,
     const bool reg = t->reg_w[0] != 0.0 || t->reg_w[1] != 0.0 || t->reg_w[2] != 0.0;
     if (reg) {
         // train.py:155-168: the three terms at this iteration's parameters; the L1/SSIM loss stays in loss[1]
-        if (ex4d_reg_forward(p[1], c.Ns, p[7], p[8], c.Nd, c.K, t->reg_w[0], t->reg_w[1], t->reg_w[2], t->reg_out, t->reg_scratch, stream))
+        if (ex4d_reg_forward(p[XYZ_DISP], c.Ns, p[XYZ_MOTION], p[ROTATION_MOTION], c.Nd, c.K, t->reg_w[0], t->reg_w[1], t->reg_w[2], t->reg_out, t->reg_scratch, stream))
             return tfail(EX4D_ERR_HIP, "regularisers: %s", ex4d_reg_last_error());
         // _xyz_disp's term joins its dense gradient; the keyframe terms are formed inside the sliced optimizer step below
-        if (c.optimizer && ex4d_reg_backward(p[1], g[1], c.Ns, nullptr, nullptr, nullptr, nullptr, 0, 1, t->reg_w[0], 0.0, 0.0, nullptr, 1, stream))
+        if (c.optimizer && ex4d_reg_backward(p[XYZ_DISP], g[XYZ_DISP], c.Ns, nullptr, nullptr, nullptr, nullptr, 0, 1, t->reg_w[0], 0.0, 0.0, nullptr, 1, stream))
             return tfail(EX4D_ERR_HIP, "regularisers: %s", ex4d_reg_last_error());
     }
     if (c.optimizer) {
@@ -286,18 +292,19 @@ int ex4d_trainer_step(Ex4dTrainer *t, double timestamp, const float *viewmatrix,
         int nd = 0, ns = 0;
         for (int i = 0; i < EX4D_TRAINER_PARAMS; i++) {
             if (t->numel[i] == 0) continue;
-            if (i == 7 || i == 8) {
+            if (i == XYZ_MOTION || i == ROTATION_MOTION) {
+                const bool motion = i == XYZ_MOTION;
                 Ex4dRadamSlicedRegTensor &sr = slr[ns++];
                 memset(&sr, 0, sizeof(sr));
                 Ex4dRadamSlicedTensor &s = sr.t;
-                sr.reg_kind = i == 7 ? 1 : 2; sr.reg_weight = t->reg_w[i == 7 ? 1 : 2]; sr.reg_rows = c.Nd;
-                s.param = p[i]; s.exp_avg = t->m[i]; s.exp_avg_sq = t->v[i]; s.rows = c.Nd; s.K = c.K; s.C = i == 7 ? 3 : 4;
+                sr.reg_kind = motion ? 1 : 2; sr.reg_weight = t->reg_w[motion ? 1 : 2]; sr.reg_rows = c.Nd;
+                s.param = p[i]; s.exp_avg = t->m[i]; s.exp_avg_sq = t->v[i]; s.rows = c.Nd; s.K = c.K; s.C = motion ? 3 : 4;
                 s.lr = c.lr[i]; s.step = t->step; s.n_windows = 1;
-                s.first[0] = t->slices[i == 7 ? 0 : 2]; s.count[0] = t->slices[i == 7 ? 1 : 3]; s.grad[0] = g[i];
+                s.first[0] = t->slices[motion ? 0 : 2]; s.count[0] = t->slices[motion ? 1 : 3]; s.grad[0] = g[i];
             } else {
                 Ex4dRadamTensor &q = dense[nd++];
                 memset(&q, 0, sizeof(q));
-                q.nan_to_num = i == 11;            // train.py:244-247: _opacity_duration_var.grad.nan_to_num() before optimizer.step()
+                q.nan_to_num = i == OPACITY_DURATION_VAR;      // train.py:244-247: its gradient goes through nan_to_num() before optimizer.step()
                 q.param = p[i]; q.grad = g[i]; q.exp_avg = t->m[i]; q.exp_avg_sq = t->v[i]; q.numel = t->numel[i]; q.lr = c.lr[i]; q.step = t->step;
             }
         }

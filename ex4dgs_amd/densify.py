@@ -17,6 +17,7 @@ import ctypes as C
 import torch
 
 from . import _C
+from .attributes import PARAM_ORDER
 
 EXPORTS = ("ex4d_densify_stats", "ex4d_densify_scratch_bytes", "ex4d_densify_plan", "ex4d_densify_apply", "ex4d_densify_last_error")
 
@@ -26,9 +27,7 @@ RULE_COPY, RULE_ZERO_NEW, RULE_CONST_NEW, RULE_CHILD_SCALING, RULE_CHILD_XYZ, RU
 MAX_TENSORS = 24
 COUNT_NAMES = ("keep", "clone", "keep_clone", "split", "split_clone", "keep_child", "keep_child_clone", "rows")
 
-STATIC_NAMES = ("_xyz", "_xyz_disp", "_rotation", "_opacity", "_scaling", "_features_dc", "_features_rest")
-DYNAMIC_NAMES = ("_xyz_motion", "_rotation_motion", "_opacity_motion", "_opacity_duration_center", "_opacity_duration_var",
-                 "_scaling_motion", "_features_dc_motion", "_features_rest_motion")
+STATIC_NAMES, DYNAMIC_NAMES = PARAM_ORDER[:7], PARAM_ORDER[7:]       # the static tensors come first
 # rows of the [9, N] statistics block (EX4D_STAT_*) and the reference's attribute names for them
 STAT_ROWS = ("gradient_accum", "denom", "error_accum", "ssim_error_accum", "error_denom", "max_radii2D", "min_radii2D", "error_min",
              "error_min_timestamp")

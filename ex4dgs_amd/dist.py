@@ -481,6 +481,7 @@ class ShardedRAdam:
         self.exchange.wait()
         for ex in self.row_exchange.values():
             ex.wait()
+        ptr = lambda x: x.data_ptr() if x.is_cuda else x       # the CPU tests' injected step functions take the tensors themselves
         items, sliced_items = [], []
         for i, (p, g) in enumerate(zip(self.params, self._grads)):
             self.steps[i] += 1
@@ -492,20 +493,16 @@ class ShardedRAdam:
                     ex = self.row_exchange[i]
                     pv = p.view(-1)[lo:hi]
                     cuda = pv.is_cuda
-                    wins = [(f, c, (t.data_ptr() if cuda else t)) for f, c, t in ex.windows()]
+                    wins = [(f, c, ptr(t)) for f, c, t in ex.windows()]
                     if not cuda:                # CPU tests: the positions are host-readable
                         firsts = ex.first.tolist()
                         wins = [(int(firsts[r]) if f is None else f, c, t) for r, (f, c, t) in enumerate(wins)]
-                    sliced_items.append((pv.data_ptr() if cuda else pv, self.exp_avg[i].data_ptr() if cuda else self.exp_avg[i],
-                                         self.exp_avg_sq[i].data_ptr() if cuda else self.exp_avg_sq[i], rows, K, Cc, self.lrs[i], self.steps[i], wins,
+                    sliced_items.append((ptr(pv), ptr(self.exp_avg[i]), ptr(self.exp_avg_sq[i]), rows, K, Cc, self.lrs[i], self.steps[i], wins,
                                          (ex.first.data_ptr() if (cuda and ex.active()) else None)))
                 continue
             if hi > lo:
                 pv, gv = p.view(-1)[lo:hi], g.view(-1)[lo:hi]
-                items.append((pv.data_ptr() if pv.is_cuda else pv, gv.data_ptr() if gv.is_cuda else gv,
-                              self.exp_avg[i].data_ptr() if pv.is_cuda else self.exp_avg[i],
-                              self.exp_avg_sq[i].data_ptr() if pv.is_cuda else self.exp_avg_sq[i], hi - lo, self.lrs[i], self.steps[i],
-                              self.nan_to_num[i]))
+                items.append((ptr(pv), ptr(gv), ptr(self.exp_avg[i]), ptr(self.exp_avg_sq[i]), hi - lo, self.lrs[i], self.steps[i], self.nan_to_num[i]))
         self.step_fn(items, self.betas, self.eps, self.device)
         if sliced_items:
             self.sliced_step_fn(sliced_items, self.betas, self.eps, self.device)

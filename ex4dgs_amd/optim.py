@@ -51,27 +51,33 @@ def _lib():
     return lib
 
 
+def _launch(descs, struct, entry, limit, betas, eps, device):
+    """`entry` over descs (a list of `struct`), at most `limit` per call, on device's current stream; a refused call raises its text."""
+    lib = _lib()
+    with torch.cuda.device(device):
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        for i in range(0, len(descs), limit):
+            chunk = descs[i:i + limit]
+            if getattr(lib, entry)((struct * len(chunk))(*chunk), len(chunk), betas[0], betas[1], eps, stream):
+                raise RuntimeError(lib.ex4d_optim_last_error().decode())
+
+
 def radam_step_raw(items, betas, eps, device):
     """One fused launch (per <= 32 tensors) over raw element ranges.  items: iterable of
     (param_ptr, grad_ptr, exp_avg_ptr, exp_avg_sq_ptr, numel, lr, step[, nan_to_num]) -- plain device pointers, so a range may be a
     whole tensor or a rank's shard of one (RAdam is element-wise: updating ranges separately gives bit-identical results).
     nan_to_num = 1 reads the gradient through torch.nan_to_num (train.py:244-247 does that to _opacity_duration_var.grad)."""
-    lib = _lib()
     descs = [Ex4dRadamTensor(int(it[0]), int(it[1]), int(it[2]), int(it[3]), int(it[4]), float(it[5]), int(it[6]), int(it[7]) if len(it) > 7 else 0, 0)
              for it in items if it[4] > 0]
-    with torch.cuda.device(device):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        for i in range(0, len(descs), MAX_TENSORS):
-            chunk = descs[i:i + MAX_TENSORS]
-            arr = (Ex4dRadamTensor * len(chunk))(*chunk)
-            if lib.ex4d_radam_step(arr, len(chunk), betas[0], betas[1], eps, stream):
-                raise RuntimeError(lib.ex4d_optim_last_error().decode())
+    _launch(descs, Ex4dRadamTensor, "ex4d_radam_step", MAX_TENSORS, betas, eps, device)
 
 
-def _sliced_descs(items):
+def _sliced_descs(items, reg=False):
+    """The descriptors of the sliced item tuples (radam_step_sliced_raw; reg: radam_step_sliced_reg_raw); tensors without rows are left out."""
     descs = []
     for it in items:
-        (p, m, v, rows, K, Cc, lr, step, windows), first_dev = it[:9], (it[9] if len(it) > 9 else None)
+        p, m, v, rows, K, Cc, lr, step, windows = it[:9]
+        first_dev = it[9] if len(it) > 9 else None
         if rows <= 0:
             continue
         if len(windows) > MAX_WINDOWS:
@@ -81,8 +87,12 @@ def _sliced_descs(items):
         first = (C.c_int32 * 8)(*([(0 if w[0] is None else int(w[0])) for w in windows] + [0] * (8 - len(windows))))
         count = (C.c_int32 * 8)(*([w[1] for w in windows] + [0] * (8 - len(windows))))
         grad = (C.c_void_p * 8)(*([int(w[2]) for w in windows] + [None] * (8 - len(windows))))
-        descs.append((Ex4dRadamSlicedTensor(int(p), int(m), int(v), int(rows), int(K), int(Cc), float(lr), int(step), len(windows), first, count, grad,
-                                            int(first_dev) if first_dev else None), it[10:]))
+        d = Ex4dRadamSlicedTensor(int(p), int(m), int(v), int(rows), int(K), int(Cc), float(lr), int(step), len(windows), first, count, grad,
+                                  int(first_dev) if first_dev else None)
+        if reg:
+            kind, weight, reg_rows = it[10:]
+            d = Ex4dRadamSlicedRegTensor(d, int(kind), 0, float(weight), int(reg_rows))
+        descs.append(d)
     return descs
 
 
@@ -92,15 +102,7 @@ def radam_step_sliced_raw(items, betas, eps, device):
     (<= 8), grad_ptr -> [rows, count, C] floats; first_dev_ptr (optional): device int32 array of the windows' first keyframes, read by
     the kernel instead of the host values (no device -> host round trip when the positions were gathered from other ranks).
     Bit-identical to radam_step_raw on the dense gradient the windows add up to."""
-    lib = _lib()
-    descs = [d for d, _ in _sliced_descs(items)]
-    with torch.cuda.device(device):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        for i in range(0, len(descs), MAX_SLICED):
-            chunk = descs[i:i + MAX_SLICED]
-            arr = (Ex4dRadamSlicedTensor * len(chunk))(*chunk)
-            if lib.ex4d_radam_step_sliced(arr, len(chunk), betas[0], betas[1], eps, stream):
-                raise RuntimeError(lib.ex4d_optim_last_error().decode())
+    _launch(_sliced_descs(items), Ex4dRadamSlicedTensor, "ex4d_radam_step_sliced", MAX_SLICED, betas, eps, device)
 
 
 def sliced_reg_rows(K, Cc):
@@ -114,18 +116,7 @@ def radam_step_sliced_reg_raw(items, betas, eps, device):
     present (None = host positions) followed by (reg_kind, reg_weight, reg_rows): REG_NONE / REG_MOTION ([rows,K,3]) / REG_ROT
     ([rows,K,4]), the term's weight of this step and the model's full dynamic count Nd (the mean is over Nd (K-1) terms; `rows` may
     be a row range).  Bit-identical to radam_step_raw on (windows scattered into zeros + regularizers.backward_raw(accumulate=1))."""
-    lib = _lib()
-    descs = []
-    for d, tail in _sliced_descs(items):
-        kind, weight, reg_rows = tail
-        descs.append(Ex4dRadamSlicedRegTensor(d, int(kind), 0, float(weight), int(reg_rows)))
-    with torch.cuda.device(device):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        for i in range(0, len(descs), MAX_SLICED):
-            chunk = descs[i:i + MAX_SLICED]
-            arr = (Ex4dRadamSlicedRegTensor * len(chunk))(*chunk)
-            if lib.ex4d_radam_step_sliced_reg(arr, len(chunk), betas[0], betas[1], eps, stream):
-                raise RuntimeError(lib.ex4d_optim_last_error().decode())
+    _launch(_sliced_descs(items, reg=True), Ex4dRadamSlicedRegTensor, "ex4d_radam_step_sliced_reg", MAX_SLICED, betas, eps, device)
 
 
 class FusedRAdam(torch.optim.Optimizer):
@@ -142,8 +133,7 @@ class FusedRAdam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        lib = _lib()
-        batches = {}                               # (device, betas, eps) -> descriptors
+        batches = {}                               # (device, betas, eps) -> (descriptor, the gradient it points into)
         touched = []                               # tensors the library writes: their autograd version counters are bumped below
         f32 = torch.float32
         for group in self.param_groups:
@@ -172,14 +162,8 @@ class FusedRAdam(torch.optim.Optimizer):
                 batches.setdefault((p.device,) + key_tail, []).append(
                     (Ex4dRadamTensor(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), lr, int(step_t.item()), 0, 0), g))
                 touched += (p, m, v)
-        for (dev, betas, eps), items in batches.items():
-            with torch.cuda.device(dev):
-                stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-                for i in range(0, len(items), MAX_TENSORS):
-                    chunk = items[i:i + MAX_TENSORS]
-                    arr = (Ex4dRadamTensor * len(chunk))(*[c[0] for c in chunk])
-                    if lib.ex4d_radam_step(arr, len(chunk), betas[0], betas[1], eps, stream):
-                        raise RuntimeError(lib.ex4d_optim_last_error().decode())
+        for (dev, betas, eps), items in batches.items():       # (a gradient made contiguous above lives in `batches` until here)
+            _launch([d for d, _ in items], Ex4dRadamTensor, "ex4d_radam_step", MAX_TENSORS, betas, eps, dev)
         # the library wrote through raw pointers: tell autograd the tensors changed (version counters), exactly what the
         # in-place torch ops of torch.optim.RAdam do -- caches keyed on parameter versions depend on it
         if touched:

@@ -12,6 +12,8 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
+from .attributes import PARAM_ORDER
+
 
 # ----------------------------------------------------------------------------------------------
 # Cameras
@@ -128,9 +130,7 @@ class DynamicGaussians:
     `_xyz_motion[Nd,K,3] _rotation_motion[Nd,K,4] _opacity_motion[Nd,1] _opacity_duration_center[Nd,2,1]
     _opacity_duration_var[Nd,2,1] _scaling_motion[Nd,3] _features_dc_motion[Nd,1,3] _features_rest_motion[Nd,15,3]`.
     """
-    PARAM_NAMES = ("_xyz", "_xyz_disp", "_rotation", "_opacity", "_scaling", "_features_dc", "_features_rest",
-                   "_xyz_motion", "_rotation_motion", "_opacity_motion", "_opacity_duration_center",
-                   "_opacity_duration_var", "_scaling_motion", "_features_dc_motion", "_features_rest_motion")
+    PARAM_NAMES = PARAM_ORDER
 
     def __init__(self, params, duration=300, interval=10, time_pad=2, var_pad=3, kernel_size=0.1, sh_degree=3, fused=False, split_sh=True):
         for n in self.PARAM_NAMES:

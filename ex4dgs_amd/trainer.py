@@ -108,10 +108,8 @@ class FrameTrainer:
         self.mode = exchange if (self.world > 1 or exchange == "sharded" or force) else "none"
         self.overlap = overlap
         self.side = torch.cuda.Stream(device=self.device) if overlap else None
+        self._group, self._force = group, force
         self.feature_idx = [self.names.index(n) for n in attr.FEATURE_NAMES]
-        # persistent gradient buffers of the 11 non-feature parameters (written once per step by the attribute backward);
-        # the four feature gradients come out of the rasterizer's SplitSH path as fresh tensors every step
-        self.pgrad = [None if i in self.feature_idx else torch.zeros_like(p) for i, p in enumerate(self.params)]
         lrs = dict(reference_lrs(spatial_lr_scale), **(lrs or {}))
         self.lrs = [lrs[n] for n in self.names]
         self.opt = None
@@ -127,13 +125,7 @@ class FrameTrainer:
         if self.sliced and not fits:
             raise ValueError(f"sliced keyframe gradients take one window per rank, at most {MAX_WINDOWS}")
         self.kf_idx = [self.names.index(n) for n in attr.SLICED_SHAPES] if self.sliced else []
-        self.kf_gather = []
-        if self.sliced:
-            for i in self.kf_idx:
-                shape = (self.params[i].shape[0],) + attr.SLICED_SHAPES[self.names[i]]
-                self.pgrad[i] = torch.zeros(shape, dtype=torch.float32, device=self.device)
-                if self.mode != "sharded":      # replicated optimizer: every rank needs every window (all-gather); sharded: row all-to-all inside ShardedRAdam
-                    self.kf_gather.append(xdist.SliceGather(shape, self.device, group=group, local_only=(self.mode != "allreduce"), force=force))
+        self._make_grad_buffers()
         # two exchanges: the four feature gradients (3/4 of the bytes) leave the rasterizer backward and are on the wire while the
         # attribute backward still runs; the other parameters follow it
         self.feat_pos = [i for i in self.feature_idx]
@@ -167,6 +159,18 @@ class FrameTrainer:
         self.last = {}
 
     # ------------------------------------------------------------------------------------------
+    def _make_grad_buffers(self):
+        """The buffers sized by the parameters' rows: pgrad, the persistent gradient buffers of the 11 non-feature parameters (written
+        once per step by the attribute backward; the four feature gradients come out of the rasterizer's SplitSH path as fresh tensors
+        every step), and kf_gather, the window gathers of the sliced keyframe tensors."""
+        self.pgrad = [None if i in self.feature_idx else torch.zeros_like(p) for i, p in enumerate(self.params)]
+        self.kf_gather = []
+        for i in self.kf_idx:
+            shape = (self.params[i].shape[0],) + attr.SLICED_SHAPES[self.names[i]]
+            self.pgrad[i] = torch.zeros(shape, dtype=torch.float32, device=self.device)
+            if self.mode != "sharded":      # replicated optimizer: every rank needs every window (all-gather); sharded: row all-to-all inside ShardedRAdam
+                self.kf_gather.append(xdist.SliceGather(shape, self.device, group=self._group, local_only=(self.mode != "allreduce"), force=self._force))
+
     def _settings(self, cam, bg, near, far):
         H, W = int(cam.image_height), int(cam.image_width)
         key = (H, W)
@@ -337,12 +341,17 @@ class FrameTrainer:
         m = self.model
         self.last["reg"] = reg.forward_raw(m._xyz_disp, m._xyz_motion, m._rotation_motion, self._reg_w, out=self._reg_out, scratch=self._reg_scratch)
 
-    def _apply_optimizer(self):
+    def _drain(self):
+        """Everything pending ends on the current stream: an asynchronous frame is settled (re-run if it overflowed), the exchange
+        finished, the side stream's attribute backward waited for."""
         if self.async_forward:
             self._settle_frame()
         self.finish_exchange()
         if self.side is not None:
             torch.cuda.current_stream(self.device).wait_stream(self.side)
+
+    def _apply_optimizer(self):
+        self._drain()
         if self.mode == "sharded":
             self.opt.step()                                # (its exchange was launched by _run_frame: launch_exchange(grads, windows))
         else:
@@ -359,21 +368,20 @@ class FrameTrainer:
                 reg.backward_raw(m_._xyz_disp, m_._xyz_motion, m_._rotation_motion, w, gi, accumulate=True)
             items = [(p.data_ptr(), g.data_ptr(), mm.data_ptr(), vv.data_ptr(), p.numel(), lr, self.steps, int(self.names[i] in NAN_TO_NUM))
                      for i, (p, g, mm, vv, lr) in enumerate(zip(self.params, self._grads, self.m, self.v, self.lrs)) if i not in self.kf_idx]
-            radam_step_raw(items, (0.9, 0.999), 1e-8, self.device)
+            hyper = ((0.9, 0.999), 1e-8, self.device)      # betas, eps: the defaults of the reference's RAdam (c_gaussian_model.py:449)
+            radam_step_raw(items, *hyper)
             if self.sliced:
                 sl = []
                 for gth, i in zip(self.kf_gather, self.kf_idx):
                     p = self.params[i]
                     count, Cc = attr.SLICED_SHAPES[self.names[i]]
-                    sl.append((p.data_ptr(), self.m[i].data_ptr(), self.v[i].data_ptr(), p.shape[0], p.shape[1], Cc, self.lrs[i], self.steps,
-                               gth.windows(count), gth.first_device_ptr()))
+                    item = (p.data_ptr(), self.m[i].data_ptr(), self.v[i].data_ptr(), p.shape[0], p.shape[1], Cc, self.lrs[i], self.steps,
+                            gth.windows(count), gth.first_device_ptr())
                     if w is not None:
                         motion = self.names[i] == "_xyz_motion"
-                        sl[-1] += (REG_MOTION if motion else REG_ROT, w[1] if motion else w[2], p.shape[0])
-                if w is not None:
-                    radam_step_sliced_reg_raw(sl, (0.9, 0.999), 1e-8, self.device)
-                else:
-                    radam_step_sliced_raw(sl, (0.9, 0.999), 1e-8, self.device)
+                        item += (REG_MOTION if motion else REG_ROT, w[1] if motion else w[2], p.shape[0])
+                    sl.append(item)
+                (radam_step_sliced_reg_raw if w is not None else radam_step_sliced_raw)(sl, *hyper)
             torch.autograd.graph.increment_version(self.params)
         self._grads = None
 
@@ -382,11 +390,7 @@ class FrameTrainer:
         if self.optimizer and self._grads is not None:
             self._apply_optimizer()
         else:
-            if self.async_forward:
-                self._settle_frame()
-            self.finish_exchange()
-            if self.side is not None:
-                torch.cuda.current_stream(self.device).wait_stream(self.side)
+            self._drain()
 
     def begin_density_control(self):
         """Before densify_and_prune / a prune (ex4dgs_amd.densify) replaces the model's tensors: settles a pending asynchronous frame and
@@ -395,11 +399,7 @@ class FrameTrainer:
         if self.mode != "none" or self.k != 1:
             raise NotImplementedError("density control on a FrameTrainer needs exchange='none' and views_per_step=1: "
                                       "multi-rank density control needs a reduction of the statistics first")
-        if self.async_forward:
-            self._settle_frame()
-        self.finish_exchange()
-        if self.side is not None:
-            torch.cuda.current_stream(self.device).wait_stream(self.side)
+        self._drain()
         self._grads = None
 
     def rebind_parameters(self, moments=None):
@@ -408,13 +408,7 @@ class FrameTrainer:
         if self._grads is not None:
             raise RuntimeError("rebind_parameters: pending gradients (call begin_density_control first)")
         self.params = [getattr(self.model, n) for n in self.names]
-        self.pgrad = [None if i in self.feature_idx else torch.zeros_like(p) for i, p in enumerate(self.params)]
-        if self.sliced:
-            self.kf_gather = []
-            for i in self.kf_idx:
-                shape = (self.params[i].shape[0],) + attr.SLICED_SHAPES[self.names[i]]
-                self.pgrad[i] = torch.zeros(shape, dtype=torch.float32, device=self.device)
-                self.kf_gather.append(xdist.SliceGather(shape, self.device, local_only=True))
+        self._make_grad_buffers()
         if self.optimizer:
             moments = moments or {}
             pairs = [moments.get(n) for n in self.names]

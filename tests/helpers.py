@@ -468,3 +468,34 @@ def compare_backward(ob, gb, fwd_o, atol=1e-5, k_eps=64.0, rel_tol=1e-5, conic=N
         assert r["max_abs"] <= bar, (f"{k}: max-abs error {r['max_abs']:.3e} is {r['rel_to_tensor_max']:.2e} of the tensor's magnitude {r['ref_max']:.3e} "
                                      f"(> {rel_tol} + 8 x stage noise {r.get('stage_noise_max', 0.0):.3e})")
     return rep
+
+
+def assert_sliced_steps_refuse_bad_descriptors(dev):
+    """ex4d_radam_step_sliced and ex4d_radam_step_sliced_reg validate a sliced tensor with the same code: each bad descriptor below is
+    refused by both with a RuntimeError -- an argument error returned before any launch -- and the parameter, exp_avg and exp_avg_sq
+    keep their bits."""
+    import pytest
+    from ex4dgs_amd import optim
+    g = torch.Generator().manual_seed(5)
+    rows, K = 5, 7
+    p, m, v, blk = [torch.rand(rows, K, 5, generator=g).to(dev) for _ in range(4)]      # room for every (C, count) named below
+    kept = [x.clone() for x in (p, m, v)]
+    win = lambda first, count: (first, count, blk.data_ptr())
+    # (text of the fault, C, step, windows)
+    bad = [(r"outside \[0, K\) or null", 3, 1, [win(6, 4)]),                    # window outside [0, K)
+           (r"outside \[0, K\) or null", 3, 1, [win(0, 4), win(-1, 4)]),
+           (r"outside \[0, K\) or null", 3, 1, [win(0, 0)]),                    # count < 1
+           ("bad shape", 5, 1, [win(0, 4)]),                                   # C = 5
+           ("step < 1", 3, 0, [win(0, 4)]),                                    # step = 0
+           ("at most 8", 3, 1, [win(0, 1)] * 9),                               # more than 8 windows
+           ("needs first_dev", 3, 1, [(None, 4, blk.data_ptr())])]             # neither a host position nor first_dev
+    for text, Cc, step, windows in bad:
+        item = (p.data_ptr(), m.data_ptr(), v.data_ptr(), rows, K, Cc, 1e-2, step, windows)
+        with pytest.raises(RuntimeError, match=text):
+            optim.radam_step_sliced_raw([item], (0.9, 0.999), 1e-8, dev)
+        kind = optim.REG_MOTION if Cc == 3 else optim.REG_NONE
+        with pytest.raises(RuntimeError, match=text):
+            optim.radam_step_sliced_reg_raw([item + (None, kind, 1e-3, rows)], (0.9, 0.999), 1e-8, dev)
+    torch.cuda.synchronize()
+    for x, x0 in zip((p, m, v), kept):
+        assert torch.equal(x, x0)

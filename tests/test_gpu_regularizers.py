@@ -262,6 +262,7 @@ def test_fused_step_without_a_regulariser_gives_the_bits_of_the_sliced_step(hip_
     big = torch.zeros(4, 2000, 3).cuda()
     with pytest.raises(RuntimeError, match="do not fit"):
         optim.radam_step_sliced_reg_raw([(big.data_ptr(), big.data_ptr(), big.data_ptr(), 4, 2000, 3, 1e-2, 1, [], None, optim.REG_MOTION, 1.0, 4)], BETAS, EPS, dev)
+    h.assert_sliced_steps_refuse_bad_descriptors(dev)
 
 
 # ------------------------------------------------------------------------------------------------ the anchor: reference lines + torch.optim.RAdam

@@ -158,6 +158,7 @@ def test_sliced_radam_is_bit_identical_to_the_dense_step(hip_lib):
             assert torch.equal(A, B) and torch.equal(mA, mB) and torch.equal(vA, vB), (rows, K, Cc, step)
     with pytest.raises(RuntimeError):
         radam_step_sliced_raw([(A.data_ptr(), mA.data_ptr(), vA.data_ptr(), 5, 7, 3, 1e-2, 1, [(6, 4, A.data_ptr())])], (0.9, 0.999), 1e-8, dev)   # window outside [0, K)
+    h.assert_sliced_steps_refuse_bad_descriptors(dev)
 
 
 def test_trainer_with_sliced_optimizer_tracks_the_dense_one(hip_lib):
