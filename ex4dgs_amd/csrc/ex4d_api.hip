@@ -412,7 +412,7 @@ static int forward_impl(
         MARK(0, "depth_sort");
         // 3. instance offsets in depth order + total: the rects arrive in depth order (rects4_b), nothing to gather
         if (!fused_scan && !rows_sort) {
-            STAGE(ex4d_launch_scan_tiles(P, nullptr, g.rects4_b, nullptr, nullptr, g.sorted_offsets, g.scan_block_sums, T, im.ranges, g.total, stream), prm, stream);
+            STAGE(ex4d_launch_scan_tiles(P, nullptr, g.rects4_b, nullptr, nullptr, g.sorted_offsets, g.scan_block_sums, T, im.ranges, async ? g.total : nullptr, stream), prm, stream);
             MARK(0, "scan_tiles");
         }
     } else {
@@ -425,8 +425,9 @@ static int forward_impl(
         if (in_first == start_in_b) return fail(EX4D_ERR_HIP, "internal: depth sort ended in the wrong buffer");
         MARK(0, "depth_sort");
         if (!lsd_gather) {
-            // 3. instance offsets in depth order + total (the total also lands in g.total[0]: device-side instance count)
-            STAGE(ex4d_launch_scan_tiles(P, g.rects, packed_rects ? g.rects4 : nullptr, g.depth_order, g.sorted_rects, g.sorted_offsets, g.scan_block_sums, T, im.ranges, g.total, stream), prm, stream);
+            // 3. instance offsets in depth order + total (asynchronous forward: the total also lands in g.total[0], the device-side instance
+            // count, which only that forward clears and reads)
+            STAGE(ex4d_launch_scan_tiles(P, g.rects, packed_rects ? g.rects4 : nullptr, g.depth_order, g.sorted_rects, g.sorted_offsets, g.scan_block_sums, T, im.ranges, async ? g.total : nullptr, stream), prm, stream);
             MARK(0, "scan_tiles");
         }
     }

@@ -882,8 +882,9 @@ __global__ __launch_bounds__(256) void scan_tiles_local_kernel(int P, const uint
     if (threadIdx.x == 255) {
         block_sums[blockIdx.x] = woff + x;
         // the frame's instance count in device memory (cleared with the frame flags): what the kernels behind this one read when the
-        // forward runs asynchronously (a few hundred fire-and-forget atomics spread over the kernel's duration)
-        atomicAdd(frame_total, woff + x);
+        // forward runs asynchronously (a few hundred fire-and-forget atomics spread over the kernel's duration).  The synchronous forward
+        // passes nullptr: it does not clear that word and nothing reads it there (written-before-read audit)
+        if (frame_total) atomicAdd(frame_total, woff + x);
     }
 }
 

@@ -18,6 +18,9 @@
  * in the reference (rasterizer_impl.h:29-65); the caller owns their storage and provides it through
  * the allocation callbacks (reference: std::function<char*(size_t)>, rasterize_points.cu:27-33).
  * Their INTERNAL layout is this library's own (ex4d_*_layout below reports it for tests).
+ * The storage behind the callbacks, the output tensors and the backward's scratch may arrive with ANY content -- uninitialised, or
+ * whatever an earlier frame of any size and any options left there: every word the library reads it has written in the same call
+ * ("Written before read"), and it writes nothing outside the byte counts it asked for / the shapes stated below.
  */
 #ifndef EX4D_RASTERIZER_H_INCLUDED
 #define EX4D_RASTERIZER_H_INCLUDED
@@ -48,8 +51,12 @@ typedef struct Ex4dParams {
                                  SH backward (36 B per visible Gaussian, inside the geometry buffer) while it has the SH rows in registers;
                                  pass the SAME value to the backward call that consumes this forward's buffers: it then does not read
                                  the SH tensors at all (-155 MB of 535 at 1.0 M Gaussians).  0 = the backward reads them itself.
-                                 The forward marks the geometry buffer when it stored the sums; a backward that asks for them on a
-                                 buffer whose forward ran with 0 returns NaN gradients (never numbers computed from uninitialised memory). */
+                                 Every forward leaves a word in the geometry buffer that says whether it stored the sums (also a forward
+                                 with 0 on storage an earlier frame with 1 used).  A backward that asks for them on buffers whose forward
+                                 ran with 0 returns dL_dmeans3D = NaN (all three components) for every visible Gaussian (radii > 0) of a
+                                 frame rendered from SH -- the one gradient the sums enter -- and every other output, dL_dmeans3D of the
+                                 invisible Gaussians (zeros) included, exactly as the backward with 0 does: never numbers computed from
+                                 uninitialised memory or from another frame's sums. */
     int32_t instance_capacity;/* 0 (default): the reference's behaviour -- the forward reads the instance count back (one blocking 4-byte D2H,
                                  rasterizer_impl.cu:298-299) and sizes the binning buffer exactly.
                                  > 0: ASYNCHRONOUS forward.  The binning buffer is sized for this many (Gaussian, tile) instances, every kernel
@@ -97,8 +104,9 @@ const char *ex4d_target_arch(void);
 /*
  * Forward: replaces CudaRasterizer::Rasterizer::forward (rasterizer_impl.cu:204-363).
  * Outputs follow rasterize_points.cu:73-78: out_color[3,H,W], radii[P] (int32), out_depth[1,H,W],
- * out_acc[1,H,W], out_flow[3,H,W], out_idx[1,H,W] (int32); all are fully written by the call
- * (no pre-initialisation needed; out_idx = -1 where nothing contributed).
+ * out_acc[1,H,W], out_flow[3,H,W], out_idx[1,H,W] (int32); every element of all six is written by the call whatever it held before
+ * (no pre-initialisation needed; out_idx = -1 where nothing contributed, radii = 0 for culled Gaussians), and the result does not
+ * depend on what the outputs or the three state buffers held: the forward is deterministic, bit for bit.
  * *num_rendered receives the number of (Gaussian, tile) instances (host int, one blocking 4-byte D2H
  * exactly like rasterizer_impl.cu:298-299).  P == 0 is handled by the caller (rasterize_points.cu:90).
  * With Ex4dParams.instance_capacity > 0 the call is asynchronous and `num_rendered` is an Ex4dFrameStatus in pinned host
@@ -129,8 +137,10 @@ int ex4d_forward(
 
 /*
  * Backward: replaces CudaRasterizer::Rasterizer::backward (rasterizer_impl.cu:367-486) including the
- * zero-fill of the ten gradient tensors (rasterize_points.cu:178-187): every output below is fully
- * written for all P Gaussians (zeros for invisible ones), so the caller may pass uninitialised memory.
+ * zero-fill of the ten gradient tensors (rasterize_points.cu:178-187): every element of every non-NULL output below is
+ * written for all P Gaussians (exact zeros in the rows of Gaussians with radii == 0), so the caller may pass uninitialised memory,
+ * also for `bwd_scratch` (the call clears it).  The three state buffers are read only: the call leaves them bit-unchanged, and
+ * may be repeated on them (a retained autograd graph).
  * dL_dcolors and dL_dcov3D may be NULL (a caller that rendered from SH / from scale + rotation has no tensor to receive them): they
  * are then not written -- 36 bytes per Gaussian less HBM traffic; every other output is required.
  * `bwd_scratch` must hold ex4d_backward_scratch_bytes(P) bytes (internal per-Gaussian accumulators,

@@ -470,6 +470,31 @@ def compare_backward(ob, gb, fwd_o, atol=1e-5, k_eps=64.0, rel_tol=1e-5, conic=N
     return rep
 
 
+def assert_per_gaussian_stage_bit_exact(o, gb, ob=None):
+    """The per-Gaussian backward stage in isolation: the GPU's own accumulators (gb["acc16"]) fed to the oracle's stage
+    (oracle.preprocess_backward on the oracle forward `o`) give the five derived gradients of `gb` bit for bit, and the three
+    gradients that ARE accumulators equal their accumulator columns.  ob (an oracle backward of the same frame, optional): its
+    arrays give the shapes of the stage's inputs and outputs; without it they are built from `o`."""
+    from oracle import oracle
+    acc = acc16_in_reference_units(gb["acc16"], o["W"], o["H"], conic=o["conic_opacity"])
+    if ob is not None:
+        res = {k: np.zeros_like(v) for k, v in ob.items() if isinstance(v, np.ndarray) and k.startswith("dL_")}
+    else:
+        P, M = o["P"], o["M"]
+        res = {k: np.zeros(s, np.float32) for k, s in (("dL_dmeans3D", (P, 3)), ("dL_dcov3D", (P, 6)), ("dL_dsh", (P, M, 3)),
+                                                       ("dL_dscales", (P, 3)), ("dL_drotations", (P, 4)))}
+    res["dL_dmeans2D"] = np.ascontiguousarray(acc[:, 0:3])
+    res["dL_dconic"] = np.ascontiguousarray(np.stack([acc[:, 3], acc[:, 4], np.zeros_like(acc[:, 3]), acc[:, 5]], -1))
+    res["dL_dcolors"] = np.ascontiguousarray(acc[:, 7:10])
+    oracle.preprocess_backward(o, res)
+    for k in ("dL_dmeans3D", "dL_dcov3D", "dL_dsh", "dL_dscales", "dL_drotations"):
+        a, b = res[k], to_np(gb[k])
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), f"{k}: per-Gaussian backward stage not bit-exact (max abs {np.abs(a - b).max()})"
+    assert np.array_equal(to_np(gb["dL_dmeans2D"]), acc[:, 0:3])
+    assert np.array_equal(to_np(gb["dL_dopacity"])[:, 0], acc[:, 6])
+    assert np.array_equal(to_np(gb["dL_ddir"]), acc[:, 10:13])
+
+
 def assert_sliced_steps_refuse_bad_descriptors(dev):
     """ex4d_radam_step_sliced and ex4d_radam_step_sliced_reg validate a sliced tensor with the same code: each bad descriptor below is
     refused by both with a RuntimeError -- an argument error returned before any launch -- and the parameter, exp_avg and exp_avg_sq

@@ -70,18 +70,7 @@ def _fwd_bwd(cfg, P=None, t=0, sh_degree=3, grad_acc_zero=False, mutate=None, su
     ob_e2e = oracle.backward(o, *grads, state_delta=dstate)
     rep["e2e"] = h.compare_backward(ob_e2e, gb, o, extra13=2.0 * ob_e2e["state13"], tag=f"{cfg if isinstance(cfg, str) else cfg.name} P={o['P']} t={t} END-TO-END")
     # per-Gaussian backward stage in isolation: feed the GPU's own accumulators to the oracle's stage
-    acc = h.acc16_in_reference_units(gb["acc16"], o["W"], o["H"], conic=o["conic_opacity"])
-    res = {k: np.zeros_like(v) for k, v in ob.items() if isinstance(v, np.ndarray) and k.startswith("dL_")}
-    res["dL_dmeans2D"] = np.ascontiguousarray(acc[:, 0:3])
-    res["dL_dconic"] = np.ascontiguousarray(np.stack([acc[:, 3], acc[:, 4], np.zeros_like(acc[:, 3]), acc[:, 5]], -1))
-    res["dL_dcolors"] = np.ascontiguousarray(acc[:, 7:10])
-    oracle.preprocess_backward(o, res)
-    for k in ("dL_dmeans3D", "dL_dcov3D", "dL_dsh", "dL_dscales", "dL_drotations"):
-        a, b = res[k], h.to_np(gb[k])
-        assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), f"{k}: per-Gaussian backward stage not bit-exact (max abs {np.abs(a - b).max()})"
-    assert np.array_equal(h.to_np(gb["dL_dmeans2D"]), acc[:, 0:3])
-    assert np.array_equal(h.to_np(gb["dL_dopacity"])[:, 0], acc[:, 6])
-    assert np.array_equal(h.to_np(gb["dL_ddir"]), acc[:, 10:13])
+    h.assert_per_gaussian_stage_bit_exact(o, gb, ob)
     return o, g, ob, gb, rep
 
 
