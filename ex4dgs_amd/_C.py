@@ -8,23 +8,14 @@ gfx950) through ctypes.  PyTorch is only used for device memory and the current 
 There is NO fallback: if the library is missing or a tensor is not on a ROCm device, the call raises.
 """
 import ctypes as C
-import os
 
 import torch
 
-_CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
-# EX4D_HIP_LIB: developer override (a variant build of the same sources, e.g. tools/dev/spill_probe.py); the product loads the in-tree library
-_LIB_PATH = os.environ.get("EX4D_HIP_LIB") or os.path.join(_CSRC, "libex4d_hip.so")
-_lib = None
+from . import _abi
+from ._abi import ALLOC_FN, BinningLayout, Ex4dParams, Ex4dSplitSH, GeomLayout, ImgLayout, library_path, load  # noqa: F401  (this module's surface)
 
 NUM_CHANNELS = 3   # cuda_rasterizer/config.h:15
-
-
-class Ex4dParams(C.Structure):
-    _fields_ = [("P", C.c_int32), ("D", C.c_int32), ("M", C.c_int32), ("W", C.c_int32), ("H", C.c_int32),
-                ("tanfovx", C.c_float), ("tanfovy", C.c_float), ("kernel_size", C.c_float), ("scale_modifier", C.c_float),
-                ("min_depth", C.c_float), ("max_depth", C.c_float), ("prefiltered", C.c_int32), ("debug", C.c_int32),
-                ("prepare_backward", C.c_int32), ("instance_capacity", C.c_int32), ("assume_no_flow", C.c_int32), ("reserved", C.c_int32)]
+EXPORTS = _abi.exports("ex4d_rasterizer.h")
 
 
 class PendingFrame:
@@ -120,22 +111,6 @@ def _pinned_status():
     return _status_pool.pop()
 
 
-class GeomLayout(C.Structure):
-    _fields_ = [(n, C.c_size_t) for n in ("records", "cov3D", "clamped", "tiles_touched", "depth_order", "sorted_offsets", "rects", "total")]
-
-
-class BinningLayout(C.Structure):
-    _fields_ = [(n, C.c_size_t) for n in ("point_list", "tile_ids", "qlist", "qcount", "total")]
-
-
-class ImgLayout(C.Structure):
-    _fields_ = [(n, C.c_size_t) for n in ("final_T", "n_contrib", "ranges", "total")]
-
-
-class Ex4dSplitSH(C.Structure):          # include/ex4d_rasterizer.h: Ex4dSplitSH / Ex4dSplitSHGrad (same layout)
-    _fields_ = [("dc", C.c_void_p * 2), ("rest", C.c_void_p * 2), ("n_static", C.c_int32)]
-
-
 class SplitSH(tuple):
     """The SH coefficients as CGaussianModel stores them -- (features_dc [Ns,1,3], features_rest [Ns,15,3],
     features_dc_motion [Nd,1,3], features_rest_motion [Nd,15,3]) -- accepted wherever the `sh` / `shs` tensor goes:
@@ -170,57 +145,6 @@ def _split_struct(split, device, what):
         raise RuntimeError(f"{what}: dc and rest must have the same number of rows")
     st = Ex4dSplitSH((C.c_void_p * 2)(ptrs[0], ptrs[2]), (C.c_void_p * 2)(ptrs[1], ptrs[3]), int(split[0].shape[0]))
     return keep, st
-
-
-ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)
-
-EXPORTS = ("ex4d_last_error", "ex4d_abi_version", "ex4d_target_arch", "ex4d_forward", "ex4d_backward",
-           "ex4d_forward_split_sh", "ex4d_backward_split_sh",
-           "ex4d_backward_scratch_bytes", "ex4d_mark_visible", "ex4d_geom_bytes", "ex4d_binning_bytes", "ex4d_img_bytes",
-           "ex4d_geom_layout", "ex4d_binning_layout", "ex4d_img_layout",
-           "ex4d_profile_enable", "ex4d_profile_read", "ex4d_set_option", "ex4d_get_option", "ex4d_debug_bwd_stats", "ex4d_debug_bwd_stats16", "ex4d_debug_rows_prof")
-
-
-def library_path():
-    return _LIB_PATH
-
-
-def load():
-    """dlopen libex4d_hip.so (built in-tree by ex4dgs_amd.build); raises if it is missing."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(_LIB_PATH):
-        raise RuntimeError(f"{_LIB_PATH} not found: build it with `python -m ex4dgs_amd.build` "
-                           "(there is no CPU / PyTorch fallback for the rasterizer)")
-    lib = C.CDLL(_LIB_PATH)
-    lib.ex4d_last_error.restype = C.c_char_p
-    lib.ex4d_target_arch.restype = C.c_char_p
-    lib.ex4d_abi_version.restype = C.c_int
-    for n in ("ex4d_backward_scratch_bytes", "ex4d_geom_bytes", "ex4d_binning_bytes", "ex4d_img_bytes"):
-        getattr(lib, n).restype = C.c_size_t
-    lib.ex4d_forward.restype = C.c_int
-    lib.ex4d_backward.restype = C.c_int
-    lib.ex4d_mark_visible.restype = C.c_int
-    lib.ex4d_forward.argtypes = ([C.POINTER(Ex4dParams)] + [C.c_void_p] * 13 + [ALLOC_FN, C.c_void_p] * 3
-                                 + [C.c_void_p] * 6 + [C.c_void_p, C.POINTER(C.c_int32)])
-    lib.ex4d_backward.argtypes = [C.POINTER(Ex4dParams), C.c_int32] + [C.c_void_p] * 32
-    lib.ex4d_forward_split_sh.restype = C.c_int
-    lib.ex4d_backward_split_sh.restype = C.c_int
-    lib.ex4d_forward_split_sh.argtypes = ([C.POINTER(Ex4dParams)] + [C.c_void_p] * 3 + [C.POINTER(Ex4dSplitSH)] + [C.c_void_p] * 8
-                                          + [ALLOC_FN, C.c_void_p] * 3 + [C.c_void_p] * 6 + [C.c_void_p, C.POINTER(C.c_int32)])
-    lib.ex4d_backward_split_sh.argtypes = ([C.POINTER(Ex4dParams), C.c_int32] + [C.c_void_p] * 3 + [C.POINTER(Ex4dSplitSH)] + [C.c_void_p] * 21
-                                           + [C.POINTER(Ex4dSplitSH)] + [C.c_void_p] * 5)
-    lib.ex4d_mark_visible.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
-    lib.ex4d_set_option.argtypes = [C.c_char_p, C.c_int]
-    lib.ex4d_get_option.argtypes = [C.c_char_p]
-    _lib = lib
-    return lib
-
-
-def _check(code):
-    if code != 0:
-        raise RuntimeError(load().ex4d_last_error().decode() or f"ex4d error {code}")
 
 
 def _dev_f32(t, name, device):
@@ -280,7 +204,7 @@ def rasterize_gaussians(background, means3D, dir3D, colors, opacity, scales, rot
     instance_capacity > 0 (keyword, not in the reference): ASYNCHRONOUS forward -- no instance-count read-back, the host does not wait,
     every launch has a host-constant grid; num_rendered comes back as a PendingFrame (capacity now, count / overflow on demand).
     assume_no_flow: with it, launch the flow-free compositing kernel (the caller's dir3D is all zeros; PendingFrame.has_flow checks)."""
-    lib = load()
+    load()
     if means3D.ndimension() != 2 or means3D.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
     _require_rocm(means3D, "means3D")
@@ -333,31 +257,23 @@ def rasterize_gaussians(background, means3D, dir3D, colors, opacity, scales, rot
         # ordinary copy after a replay -- a pinned destination of a captured copy was observed to be clobbered between replays)
         status = torch.zeros(8, dtype=torch.int32, device=dev) if torch.cuda.is_current_stream_capturing() else _pinned_status()
         count_ref = C.cast(status.data_ptr(), C.POINTER(C.c_int32))
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
-        if split is not None:
-            if colors.numel() != 0:
-                raise RuntimeError("Please provide excatly one of either SHs or precomputed colors!")
-            kp, st = _split_struct(split, dev, "sh")
-            keep.append(kp)
-            code = lib.ex4d_forward_split_sh(
-                C.byref(prm), ptr["background"], ptr["means3D"], ptr["dir3D"], C.byref(st), ptr["opacity"],
-                ptr["scales"], ptr["rotations"], ptr["cov3D_precomp"], ptr["viewmatrix"], ptr["projmatrix"], ptr["campos"],
-                ptr["subpixel_offset"], cbs[0], None, cbs[1], None, cbs[2], None,
-                out_color.data_ptr(), radii.data_ptr(), out_depth.data_ptr(), out_acc.data_ptr(), out_flow.data_ptr(), out_idx.data_ptr(),
-                C.c_void_p(stream), count_ref)
-        else:
-            code = lib.ex4d_forward(
-                C.byref(prm), ptr["background"], ptr["means3D"], ptr["dir3D"], ptr["sh"], ptr["colors"], ptr["opacity"],
-                ptr["scales"], ptr["rotations"], ptr["cov3D_precomp"], ptr["viewmatrix"], ptr["projmatrix"], ptr["campos"],
-                ptr["subpixel_offset"], cbs[0], None, cbs[1], None, cbs[2], None,
-                out_color.data_ptr(), radii.data_ptr(), out_depth.data_ptr(), out_acc.data_ptr(), out_flow.data_ptr(), out_idx.data_ptr(),
-                C.c_void_p(stream), count_ref)
+    entry, sh_args = "ex4d_forward", (ptr["sh"], ptr["colors"])
+    if split is not None:
+        if colors.numel() != 0:
+            raise RuntimeError("Please provide excatly one of either SHs or precomputed colors!")
+        kp, st = _split_struct(split, dev, "sh")
+        keep.append(kp)
+        entry, sh_args = "ex4d_forward_split_sh", (C.byref(st),)      # the twin differs in the SH arguments only
+    with _abi.stream(dev) as stream:
+        _abi.call(entry, C.byref(prm), ptr["background"], ptr["means3D"], ptr["dir3D"], *sh_args, ptr["opacity"],
+                  ptr["scales"], ptr["rotations"], ptr["cov3D_precomp"], ptr["viewmatrix"], ptr["projmatrix"], ptr["campos"],
+                  ptr["subpixel_offset"], cbs[0], None, cbs[1], None, cbs[2], None,
+                  out_color.data_ptr(), radii.data_ptr(), out_depth.data_ptr(), out_acc.data_ptr(), out_flow.data_ptr(), out_idx.data_ptr(),
+                  stream, count_ref)
         ev = None
-        if status is not None and code == 0 and not torch.cuda.is_current_stream_capturing():
+        if status is not None and not torch.cuda.is_current_stream_capturing():
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream())
-    _check(code)
     if status is not None:
         return (PendingFrame(instance_capacity, assume_no_flow, status, ev, _status_pool), out_color, radii, geomBuffer, binningBuffer, imgBuffer,
                 out_depth, out_acc, out_flow, out_idx)
@@ -405,7 +321,6 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
         outs[1] = torch.empty(0, **f32)
     if not need_cov3D:
         outs[4] = torch.empty(0, **f32)
-    optr = lambda t: t.data_ptr() if t.numel() else None
     if split is not None:
         outs[5] = SplitSH(*[torch.empty_like(t, memory_format=torch.contiguous_format) for t in split])
     keep = []
@@ -420,36 +335,22 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     radii_c = radii.contiguous()
     # prepared: the forward that produced geomBuffer left the SH direction sums in it (the backward then does not read the SH tensors)
     scratch = torch.empty(lib.ex4d_backward_scratch_bytes(P), dtype=torch.uint8, device=dev)
-    scratch_ptr = scratch.data_ptr()
     prm = _params(P, int(degree), M, W, H, tan_fovx, tan_fovy, kernel_size, scale_modifier, min_depth, max_depth, False, debug, prepared)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
-        if split is not None:
-            kp, st = _split_struct(split, dev, "sh")
-            kg, gst = _split_struct(outs[5], dev, "dL_dsh")
-            keep += [kp, kg]
-            code = lib.ex4d_backward_split_sh(
-                C.byref(prm), C.c_int32(int(R)), ptr["background"], ptr["means3D"], radii_c.data_ptr(), C.byref(st),
-                ptr["scales"], ptr["rotations"], ptr["cov3D_precomp"], ptr["viewmatrix"], ptr["projmatrix"], ptr["campos"],
-                ptr["subpixel_offset"], ptr["acc_depth"], ptr["acc"],
-                geomBuffer.data_ptr(), binningBuffer.data_ptr(), imageBuffer.data_ptr(),
-                ptr["dL_dout_color"], ptr["dL_dout_depth"], ptr["dL_grad_out_flow"], ptr["dL_grad_out_acc"],
-                outs[0].data_ptr(), optr(outs[1]), outs[2].data_ptr(), outs[3].data_ptr(), optr(outs[4]),
-                C.byref(gst), outs[6].data_ptr(), outs[7].data_ptr(), outs[8].data_ptr(),
-                scratch_ptr, C.c_void_p(stream))
-            _check(code)
-            rasterize_gaussians_backward.last_scratch = scratch
-            return tuple(outs)
-        code = lib.ex4d_backward(
-            C.byref(prm), C.c_int32(int(R)), ptr["background"], ptr["means3D"], radii_c.data_ptr(), ptr["sh"], ptr["colors"],
-            ptr["scales"], ptr["rotations"], ptr["cov3D_precomp"], ptr["viewmatrix"], ptr["projmatrix"], ptr["campos"],
-            ptr["subpixel_offset"], ptr["acc_depth"], ptr["acc"],
-            geomBuffer.data_ptr(), binningBuffer.data_ptr(), imageBuffer.data_ptr(),
-            ptr["dL_dout_color"], ptr["dL_dout_depth"], ptr["dL_grad_out_flow"], ptr["dL_grad_out_acc"],
-            outs[0].data_ptr(), optr(outs[1]), outs[2].data_ptr(), outs[3].data_ptr(), optr(outs[4]),
-            outs[5].data_ptr() if M > 0 else None, outs[6].data_ptr(), outs[7].data_ptr(), outs[8].data_ptr(),
-            scratch_ptr, C.c_void_p(stream))
-    _check(code)
+    if split is None:
+        entry, sh_args, g_sh = "ex4d_backward", (ptr["sh"], ptr["colors"]), (outs[5].data_ptr() if M > 0 else None)
+    else:                                            # the twin differs in the SH arguments only
+        kp, st = _split_struct(split, dev, "sh")
+        kg, gst = _split_struct(outs[5], dev, "dL_dsh")
+        keep += [kp, kg]
+        entry, sh_args, g_sh = "ex4d_backward_split_sh", (C.byref(st),), C.byref(gst)
+    with _abi.stream(dev) as stream:
+        _abi.call(entry, C.byref(prm), int(R), ptr["background"], ptr["means3D"], radii_c.data_ptr(), *sh_args,
+                  ptr["scales"], ptr["rotations"], ptr["cov3D_precomp"], ptr["viewmatrix"], ptr["projmatrix"], ptr["campos"],
+                  ptr["subpixel_offset"], ptr["acc_depth"], ptr["acc"],
+                  geomBuffer.data_ptr(), binningBuffer.data_ptr(), imageBuffer.data_ptr(),
+                  ptr["dL_dout_color"], ptr["dL_dout_depth"], ptr["dL_grad_out_flow"], ptr["dL_grad_out_acc"],
+                  outs[0].data_ptr(), _abi.ptr(outs[1]), outs[2].data_ptr(), outs[3].data_ptr(), _abi.ptr(outs[4]),
+                  g_sh, outs[6].data_ptr(), outs[7].data_ptr(), outs[8].data_ptr(), scratch.data_ptr(), stream)
     rasterize_gaussians_backward.last_scratch = scratch      # kept for parity tests (internal accumulators)
     return tuple(outs)
 
@@ -458,7 +359,7 @@ def mark_visible(means3D, viewmatrix, projmatrix, min_depth, max_depth=3.4028234
     """markVisible (rasterize_points.cu:236-259).  The reference's Python wrapper passes 4 arguments to a
     5-argument C++ function (diff_gaussian_rasterization_df/__init__.py:207-211) and therefore cannot be
     called; here max_depth defaults to FLT_MAX so the 4-argument call works."""
-    lib = load()
+    load()
     _require_rocm(means3D, "means3D")
     dev = means3D.device
     P = means3D.size(0)
@@ -470,9 +371,8 @@ def mark_visible(means3D, viewmatrix, projmatrix, min_depth, max_depth=3.4028234
     (m, _), (v, _), (p, _) = _dev_f32(means3D, "means3D", dev), _dev_f32(viewmatrix, "viewmatrix", dev), _dev_f32(projmatrix, "projmatrix", dev)
     if v is None or p is None or v.numel() != 16 or p.numel() != 16:
         raise RuntimeError("viewmatrix and projmatrix must be 4x4 float32 tensors")
-    with torch.cuda.device(dev):
-        _check(lib.ex4d_mark_visible(P, m.data_ptr(), v.data_ptr(), p.data_ptr(), C.c_float(min_depth), C.c_float(max_depth),
-                                     present.data_ptr(), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    with _abi.stream(dev) as stream:
+        _abi.call("ex4d_mark_visible", P, m.data_ptr(), v.data_ptr(), p.data_ptr(), min_depth, max_depth, present.data_ptr(), stream)
     return present
 
 
@@ -515,7 +415,7 @@ def img_views(imgBuffer, W, H):
 
 def set_option(name, value):
     """Tuning knobs of include/ex4d_rasterizer.h (e.g. "composite_bwd_variant")."""
-    _check(load().ex4d_set_option(name.encode(), int(value)))
+    _abi.call("ex4d_set_option", name.encode(), int(value))
 
 
 def get_option(name):
@@ -528,10 +428,7 @@ def bwd_stats(reset=True, extended=False):
     ex4d_debug_bwd_stats16 (include/ex4d_rasterizer.h lists them)."""
     n = 16 if extended else 8
     buf = (C.c_ulonglong * n)()
-    fn = load().ex4d_debug_bwd_stats16 if extended else load().ex4d_debug_bwd_stats
-    rc = fn(buf, int(bool(reset)))
-    if rc != 0:
-        raise RuntimeError("ex4d_debug_bwd_stats failed")
+    _abi.call("ex4d_debug_bwd_stats16" if extended else "ex4d_debug_bwd_stats", buf, int(bool(reset)))
     return [int(x) for x in buf]
 
 

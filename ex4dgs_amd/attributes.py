@@ -11,19 +11,15 @@ import ctypes as C
 
 import torch
 
-from . import _C
+from . import _abi
+from ._abi import Ex4dAttrParams, ptr as _ptr
+from ._abi import load as _lib                      # the bound handle, for callers that drive an entry point themselves
 
 PARAM_ORDER = ("_xyz", "_xyz_disp", "_rotation", "_opacity", "_scaling", "_features_dc", "_features_rest",
                "_xyz_motion", "_rotation_motion", "_opacity_motion", "_opacity_duration_center",
                "_opacity_duration_var", "_scaling_motion", "_features_dc_motion", "_features_rest_motion")
 
-EXPORTS = ("ex4d_attributes_forward", "ex4d_attributes_backward", "ex4d_attributes_backward_sliced", "ex4d_attributes_last_error")
-
-
-class Ex4dAttrParams(C.Structure):
-    _fields_ = [("Ns", C.c_int32), ("Nd", C.c_int32), ("K", C.c_int32), ("k", C.c_int32), ("t", C.c_float), ("duration", C.c_float),
-                ("delta", C.c_float), ("h00", C.c_float), ("h10", C.c_float), ("h01", C.c_float), ("h11", C.c_float),
-                ("tau", C.c_float), ("var_min", C.c_float)]
+EXPORTS = _abi.exports("ex4d_attributes.h")
 
 
 def time_scalars(t, Ns, Nd, K, duration, interval, time_shift, var_pad):
@@ -38,24 +34,6 @@ def time_scalars(t, Ns, Nd, K, duration, interval, time_shift, var_pad):
     return Ex4dAttrParams(Ns, Nd, K, k, float(t), float(max(duration, 1)), d, h00, h10, h01, h11, tp / interval, var_pad / interval)
 
 
-def _lib():
-    lib = _C.load()
-    if not getattr(lib, "_attr_ready", False):
-        lib.ex4d_attributes_last_error.restype = C.c_char_p
-        lib.ex4d_attributes_forward.restype = C.c_int
-        lib.ex4d_attributes_backward.restype = C.c_int
-        lib.ex4d_attributes_forward.argtypes = [C.POINTER(Ex4dAttrParams)] + [C.c_void_p] * 21
-        lib.ex4d_attributes_backward.argtypes = [C.POINTER(Ex4dAttrParams)] + [C.c_void_p] * 28
-        lib.ex4d_attributes_backward_sliced.restype = C.c_int
-        lib.ex4d_attributes_backward_sliced.argtypes = [C.POINTER(Ex4dAttrParams)] + [C.c_void_p] * 27 + [C.POINTER(C.c_int32), C.c_void_p]
-        lib._attr_ready = True
-    return lib
-
-
-def _ptr(t):
-    return None if t is None or t.numel() == 0 else t.data_ptr()
-
-
 FEATURE_NAMES = ("_features_dc", "_features_rest", "_features_dc_motion", "_features_rest_motion")
 _BWD_INPUTS = ("_opacity", "_scaling", "_rotation_motion", "_opacity_motion", "_opacity_duration_center", "_opacity_duration_var", "_scaling_motion")
 
@@ -63,7 +41,6 @@ _BWD_INPUTS = ("_opacity", "_scaling", "_rotation_motion", "_opacity_motion", "_
 def forward_raw(scal, params, with_shs=True):
     """One launch of ex4d_attributes_forward on the current stream.  params: the 15 tensors in PARAM_ORDER (contiguous float32, one
     ROCm device).  Returns [means3D, rotations, opacities, scales, shs-or-empty]; no autograd."""
-    lib = _lib()
     dev = params[0].device
     if not params[0].is_cuda:
         raise RuntimeError(f"parameters are on {dev}: the fused attribute evaluation only runs on a ROCm GPU (no CPU fallback)")
@@ -74,11 +51,8 @@ def forward_raw(scal, params, with_shs=True):
     f32 = dict(dtype=torch.float32, device=dev)
     outs = [torch.empty(N, 3, **f32), torch.empty(N, 4, **f32), torch.empty(N, 1, **f32), torch.empty(N, 3, **f32),
             torch.empty(N, 16, 3, **f32) if with_shs else torch.empty(0, **f32)]
-    with torch.cuda.device(dev):
-        rc = lib.ex4d_attributes_forward(C.byref(scal), *[_ptr(x) for x in params], *[_ptr(o) for o in outs],
-                                         C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc:
-        raise RuntimeError(lib.ex4d_attributes_last_error().decode())
+    with _abi.stream(dev) as stream:
+        _abi.call("ex4d_attributes_forward", C.byref(scal), *[_ptr(x) for x in params], *[_ptr(o) for o in outs], stream)
     return outs
 
 
@@ -92,7 +66,6 @@ def backward_raw(scal, params, grads_in, with_shs=True, out=None, sliced=False):
     (None = zeros; the shs entry is ignored when with_shs is False).  out: optional list of 15 preallocated gradient tensors
     (PARAM_ORDER; None entries are allocated) -- every one is written exactly once, dense.  Returns the 15 gradients (None for the
     feature tensors when with_shs is False: their gradient comes out of the rasterizer's SplitSH path)."""
-    lib = _lib()
     dev = params[0].device
     N = scal.Ns + scal.Nd
     f32 = dict(dtype=torch.float32, device=dev)
@@ -114,16 +87,12 @@ def backward_raw(scal, params, grads_in, with_shs=True, out=None, sliced=False):
                 gout.append(torch.empty(shape, **f32))
     byname = dict(zip(PARAM_ORDER, params))
     hint = (C.c_int32 * 4)()
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    tensors = [_ptr(byname[n]) for n in _BWD_INPUTS] + [_ptr(g) for g in gin] + [_ptr(g) for g in gout]
+    with _abi.stream(dev) as stream:
         if sliced:
-            rc = lib.ex4d_attributes_backward_sliced(C.byref(scal), *[_ptr(byname[n]) for n in _BWD_INPUTS],
-                                                     *[_ptr(g) for g in gin], *[_ptr(g) for g in gout], hint, stream)
+            _abi.call("ex4d_attributes_backward_sliced", C.byref(scal), *tensors, hint, stream)
         else:
-            rc = lib.ex4d_attributes_backward(C.byref(scal), *[_ptr(byname[n]) for n in _BWD_INPUTS],
-                                              *[_ptr(g) for g in gin], *[_ptr(g) for g in gout], stream)
-    if rc:
-        raise RuntimeError(lib.ex4d_attributes_last_error().decode())
+            _abi.call("ex4d_attributes_backward", C.byref(scal), *tensors, stream)
     return (gout, tuple(int(v) for v in hint)) if sliced else gout
 
 

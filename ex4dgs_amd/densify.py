@@ -16,10 +16,11 @@ import ctypes as C
 
 import torch
 
-from . import _C
+from . import _abi
+from ._abi import Ex4dDensifyApplyGroup, Ex4dDensifyPlanGroup, Ex4dDensifyTensor, ptr
 from .attributes import PARAM_ORDER
 
-EXPORTS = ("ex4d_densify_stats", "ex4d_densify_scratch_bytes", "ex4d_densify_plan", "ex4d_densify_apply", "ex4d_densify_last_error")
+EXPORTS = _abi.exports("ex4d_densify.h")
 
 PRUNE_STATS, GRAD_STATS, L1_STATS = 1, 2, 4
 PLAN_DENSIFY, PLAN_PRUNE_INVISIBLE, PLAN_PRUNE_SMALL, PLAN_PRUNE_NAN = 0, 1, 2, 3
@@ -38,55 +39,6 @@ DYNAMIC_STAT_NAMES = ("motion_xyz_gradient_accum", "motion_denom", "motion_xyz_e
                       "motion_max_radii2D", "motion_min_radii2D", "motion_xyz_error_min", "motion_xyz_error_min_timestamp")
 # [N] (radii) versus [N, 1] (everything else) views, as the reference allocates them (c_gaussian_model.py:408-428, :843-844)
 _FLAT_STATS = ("max_radii2D", "min_radii2D")
-
-
-class Ex4dDensifyPlanGroup(C.Structure):
-    _fields_ = [("n", C.c_int64), ("stats", C.c_void_p), ("scaling", C.c_void_p), ("opacity", C.c_void_p), ("xyz", C.c_void_p),
-                ("xyz_width", C.c_int32), ("use_screen", C.c_int32), ("grad_thr", C.c_float), ("dense_scale", C.c_float),
-                ("big_scale", C.c_float), ("screen_size", C.c_float), ("min_opacity", C.c_float), ("l1_thres", C.c_float),
-                ("max_ssim", C.c_float), ("reserved", C.c_int32), ("map", C.c_void_p), ("counts", C.c_void_p), ("scratch", C.c_void_p)]
-
-
-class Ex4dDensifyTensor(C.Structure):
-    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("rows", C.c_int64), ("dst_rows", C.c_int64), ("width", C.c_int32),
-                ("planes", C.c_int32), ("rule", C.c_int32), ("group", C.c_int32), ("aux0", C.c_void_p), ("aux1", C.c_void_p),
-                ("value", C.c_float), ("reserved", C.c_int32)]
-
-
-class Ex4dDensifyApplyGroup(C.Structure):
-    _fields_ = [("map", C.c_void_p), ("child_stride", C.c_int64), ("n_split", C.c_int64), ("split_z", C.c_void_p), ("split_c1", C.c_void_p),
-                ("split_c0", C.c_void_p), ("clone_c1", C.c_void_p), ("clone_c0", C.c_void_p), ("min_len", C.c_float), ("center_lo", C.c_float),
-                ("center_hi", C.c_float), ("split_div", C.c_float)]
-
-
-def _lib():
-    lib = _C.load()
-    if not getattr(lib, "_densify_ready", False):
-        lib.ex4d_densify_last_error.restype = C.c_char_p
-        lib.ex4d_densify_stats.restype = C.c_int
-        lib.ex4d_densify_stats.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
-                                           C.c_int32, C.c_void_p]
-        lib.ex4d_densify_scratch_bytes.restype = C.c_size_t
-        lib.ex4d_densify_scratch_bytes.argtypes = [C.c_int64]
-        lib.ex4d_densify_plan.restype = C.c_int
-        lib.ex4d_densify_plan.argtypes = [C.c_int32, C.POINTER(Ex4dDensifyPlanGroup), C.c_void_p]
-        lib.ex4d_densify_apply.restype = C.c_int
-        lib.ex4d_densify_apply.argtypes = [C.POINTER(Ex4dDensifyTensor), C.c_int32, C.POINTER(Ex4dDensifyApplyGroup), C.c_void_p]
-        lib._densify_ready = True
-    return lib
-
-
-def _check(lib, code):
-    if code:
-        raise RuntimeError(lib.ex4d_densify_last_error().decode() or f"ex4d_densify error {code}")
-
-
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None and t.numel() > 0 else None
 
 
 def densify_thresholds(iteration, opt):
@@ -137,9 +89,9 @@ class DensityStats:
                 raise RuntimeError("DensityStats.update: inputs must be contiguous device tensors with one row per Gaussian")
         if radii.dtype != torch.int32 or viewspace_grad.dtype != torch.float32 or (error_grad is not None and error_grad.dtype != torch.float32):
             raise RuntimeError("DensityStats.update: radii int32, gradients float32")
-        lib = _lib()
-        _check(lib, lib.ex4d_densify_stats(_ptr(self.static), ns, _ptr(self.dynamic), nd, radii.data_ptr(), viewspace_grad.data_ptr(),
-                                           _ptr(error_grad), float(timestamp), flags, _stream(radii.device)))
+        with _abi.stream(radii.device) as stream:
+            _abi.call("ex4d_densify_stats", ptr(self.static), ns, ptr(self.dynamic), nd, radii.data_ptr(), viewspace_grad.data_ptr(),
+                      ptr(error_grad), float(timestamp), flags, stream)
 
 
 # ---------------------------------------------------------------------------------------------------- optimizer adapters
@@ -197,35 +149,34 @@ def _prepare(opt):
 
 # ---------------------------------------------------------------------------------------------------- plan + apply
 def _plan(mode, stats_block, n, device, scaling=None, opacity=None, xyz=None, thr=None):
-    lib = _lib()
     g = Ex4dDensifyPlanGroup()
     g.n = n
     mp = torch.empty(max(n, 1), 8, dtype=torch.int32, device=device)
     counts = torch.zeros(8, dtype=torch.int32, device=device)
-    scratch = torch.empty(max(int(lib.ex4d_densify_scratch_bytes(n)), 1), dtype=torch.uint8, device=device)
-    g.stats, g.map, g.counts, g.scratch = _ptr(stats_block), mp.data_ptr(), counts.data_ptr(), scratch.data_ptr()
+    scratch = torch.empty(max(int(_abi.load().ex4d_densify_scratch_bytes(n)), 1), dtype=torch.uint8, device=device)
+    g.stats, g.map, g.counts, g.scratch = ptr(stats_block), mp.data_ptr(), counts.data_ptr(), scratch.data_ptr()
     if scaling is not None:
-        g.scaling, g.opacity = _ptr(scaling), _ptr(opacity)
+        g.scaling, g.opacity = ptr(scaling), ptr(opacity)
     if xyz is not None:
-        g.xyz, g.xyz_width = _ptr(xyz), (xyz[0].numel() if n else 1)
+        g.xyz, g.xyz_width = ptr(xyz), (xyz[0].numel() if n else 1)
     for k, v in (thr or {}).items():
         setattr(g, k, v)
-    _check(lib, lib.ex4d_densify_plan(mode, C.byref(g), _stream(device)))
+    with _abi.stream(device) as stream:
+        _abi.call("ex4d_densify_plan", mode, C.byref(g), stream)
     return mp, counts, scratch
 
 
 def _apply(descs, groups, device):
-    lib = _lib()
     garr = (Ex4dDensifyApplyGroup * 2)(*groups)
-    for i in range(0, len(descs), MAX_TENSORS):
-        chunk = descs[i:i + MAX_TENSORS]
-        arr = (Ex4dDensifyTensor * len(chunk))(*chunk)
-        _check(lib, lib.ex4d_densify_apply(arr, len(chunk), garr, _stream(device)))
+    with _abi.stream(device) as stream:
+        for i in range(0, len(descs), MAX_TENSORS):
+            chunk = descs[i:i + MAX_TENSORS]
+            _abi.call("ex4d_densify_apply", (Ex4dDensifyTensor * len(chunk))(*chunk), len(chunk), garr, stream)
 
 
 def _desc(src, dst, rows, dst_rows, rule=RULE_COPY, group=0, planes=1, aux0=None, aux1=None, value=0.0):
     width = src.numel() // max(rows * planes, 1) if rows else 1
-    return Ex4dDensifyTensor(_ptr(src), _ptr(dst), rows, dst_rows, width, planes, rule, group, _ptr(aux0), _ptr(aux1), float(value), 0)
+    return Ex4dDensifyTensor(ptr(src), ptr(dst), rows, dst_rows, width, planes, rule, group, ptr(aux0), ptr(aux1), float(value), 0)
 
 
 def _gather(model, stats, opt, plans, counts, rules, groups, names_by_group):
@@ -281,7 +232,7 @@ def _groups(plans, counts, noise=None, model=None):
             for k in ("split_z", "split_c1", "split_c0", "clone_c1", "clone_c0"):
                 t = noise[gi].get(k)
                 # an empty draw tensor is never read (its count is 0): a valid one-element stand-in keeps the pointer checks simple
-                setattr(g, k, _ptr(t) if t is not None and t.numel() else _ptr(_dummy(plans[0][0].device)))
+                setattr(g, k, ptr(t) if t is not None and t.numel() else ptr(_dummy(plans[0][0].device)))
         out.append(g)
     return out
 

@@ -8,15 +8,15 @@ include/ex4d_loss.h, instead of the reference's l1_loss + ssim and their autogra
 `loss` is differentiable w.r.t. `image`; the two [H,W] error maps are the per-pixel channel means the reference hands
 to its densification statistics (train.py:149-150) and carry no gradient.  No CPU fallback.
 """
-import ctypes as C
 import math
 
 import numpy as np
 import torch
 
-from . import _C
+from . import _abi
+from ._abi import load as _lib
 
-EXPORTS = ("ex4d_loss_last_error", "ex4d_l1_ssim_scratch_floats", "ex4d_l1_ssim_forward", "ex4d_l1_ssim_backward")
+EXPORTS = _abi.exports("ex4d_loss.h")
 WINDOW_SIZE = 11
 
 
@@ -27,20 +27,6 @@ def gaussian_window(window_size=WINDOW_SIZE, sigma=1.5):
 
 
 _WINDOW = gaussian_window()
-
-
-def _lib():
-    lib = _C.load()
-    if not getattr(lib, "_loss_ready", False):
-        lib.ex4d_loss_last_error.restype = C.c_char_p
-        lib.ex4d_l1_ssim_scratch_floats.restype = C.c_size_t
-        lib.ex4d_l1_ssim_scratch_floats.argtypes = [C.c_int32, C.c_int32]
-        lib.ex4d_l1_ssim_forward.restype = C.c_int
-        lib.ex4d_l1_ssim_forward.argtypes = [C.c_int32] * 3 + [C.c_void_p] * 2 + [C.c_float] + [C.c_void_p] * 7
-        lib.ex4d_l1_ssim_backward.restype = C.c_int
-        lib.ex4d_l1_ssim_backward.argtypes = [C.c_int32] * 3 + [C.c_void_p] * 2 + [C.c_float] + [C.c_void_p] * 5
-        lib._loss_ready = True
-    return lib
 
 
 class _L1SSIM(torch.autograd.Function):
@@ -58,12 +44,9 @@ class _L1SSIM(torch.autograd.Function):
         l1e, sse = errors if errors is not None else (torch.empty(H, W, **f32), torch.empty(H, W, **f32))
         dmaps = torch.empty(3, Cn, H, W, **f32)
         scratch = torch.empty(lib.ex4d_l1_ssim_scratch_floats(H, W), **f32)
-        with torch.cuda.device(image.device):
-            rc = lib.ex4d_l1_ssim_forward(Cn, H, W, image.data_ptr(), gt.data_ptr(), float(lambda_dssim), _WINDOW.ctypes.data,
-                                          loss.data_ptr(), l1e.data_ptr(), sse.data_ptr(), dmaps.data_ptr(), scratch.data_ptr(),
-                                          C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        if rc:
-            raise RuntimeError(lib.ex4d_loss_last_error().decode())
+        with _abi.stream(image.device) as stream:
+            _abi.call("ex4d_l1_ssim_forward", Cn, H, W, image.data_ptr(), gt.data_ptr(), float(lambda_dssim), _WINDOW.ctypes.data,
+                      loss.data_ptr(), l1e.data_ptr(), sse.data_ptr(), dmaps.data_ptr(), scratch.data_ptr(), stream)
         ctx.lam = float(lambda_dssim)
         ctx.save_for_backward(image, gt, dmaps)
         ctx.mark_non_differentiable(l1e, sse)
@@ -71,16 +54,13 @@ class _L1SSIM(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_loss, _g1, _g2):
-        lib = _lib()
         image, gt, dmaps = ctx.saved_tensors
         Cn, H, W = image.shape
         g = g_loss.reshape(1).to(torch.float32).contiguous()
         grad = torch.empty_like(image)
-        with torch.cuda.device(image.device):
-            rc = lib.ex4d_l1_ssim_backward(Cn, H, W, image.data_ptr(), gt.data_ptr(), ctx.lam, _WINDOW.ctypes.data, dmaps.data_ptr(),
-                                           g.data_ptr(), grad.data_ptr(), C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        if rc:
-            raise RuntimeError(lib.ex4d_loss_last_error().decode())
+        with _abi.stream(image.device) as stream:
+            _abi.call("ex4d_l1_ssim_backward", Cn, H, W, image.data_ptr(), gt.data_ptr(), ctx.lam, _WINDOW.ctypes.data, dmaps.data_ptr(),
+                      g.data_ptr(), grad.data_ptr(), stream)
         return grad, None, None, None
 
 

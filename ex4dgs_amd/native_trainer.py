@@ -12,56 +12,13 @@ import math
 
 import torch
 
-from . import _C
+from . import _abi
 from . import attributes as attr
+from ._abi import Ex4dTrainerConfig, load as _lib
 from .loss import _WINDOW
 from .trainer import reference_lrs
 
-EXPORTS = ("ex4d_trainer_last_error", "ex4d_trainer_create", "ex4d_trainer_destroy", "ex4d_trainer_step", "ex4d_trainer_output",
-           "ex4d_trainer_grad", "ex4d_trainer_read", "ex4d_trainer_bytes", "ex4d_trainer_time_scalars", "ex4d_trainer_set_lr",
-           "ex4d_trainer_set_sh_degree", "ex4d_trainer_set_async", "ex4d_trainer_replays", "ex4d_trainer_set_regularizers")
-
-
-class Ex4dTrainerConfig(C.Structure):
-    _fields_ = [("Ns", C.c_int32), ("Nd", C.c_int32), ("K", C.c_int32), ("W", C.c_int32), ("H", C.c_int32), ("sh_degree", C.c_int32),
-                ("tanfovx", C.c_float), ("tanfovy", C.c_float), ("kernel_size", C.c_float), ("min_depth", C.c_float), ("max_depth", C.c_float),
-                ("duration", C.c_double), ("interval", C.c_double), ("time_shift", C.c_double), ("var_pad", C.c_double),
-                ("lambda_dssim", C.c_float), ("window", C.c_float * 11), ("lr", C.c_double * 15),
-                ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("optimizer", C.c_int32)]
-
-
-def _lib():
-    lib = _C.load()
-    if not getattr(lib, "_trainer_ready", False):
-        lib.ex4d_trainer_last_error.restype = C.c_char_p
-        lib.ex4d_trainer_create.restype = C.c_void_p
-        lib.ex4d_trainer_create.argtypes = [C.POINTER(Ex4dTrainerConfig), C.POINTER(C.c_void_p)]
-        lib.ex4d_trainer_destroy.restype = None
-        lib.ex4d_trainer_destroy.argtypes = [C.c_void_p]
-        lib.ex4d_trainer_step.restype = C.c_int
-        lib.ex4d_trainer_step.argtypes = [C.c_void_p, C.c_double] + [C.c_void_p] * 6 + [C.POINTER(C.c_int32)]
-        lib.ex4d_trainer_output.restype = C.c_void_p
-        lib.ex4d_trainer_output.argtypes = [C.c_void_p, C.c_int32]
-        lib.ex4d_trainer_grad.restype = C.c_void_p
-        lib.ex4d_trainer_grad.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
-        lib.ex4d_trainer_read.restype = C.c_int
-        lib.ex4d_trainer_read.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]
-        lib.ex4d_trainer_time_scalars.restype = None
-        lib.ex4d_trainer_time_scalars.argtypes = [C.POINTER(Ex4dTrainerConfig), C.c_double, C.POINTER(attr.Ex4dAttrParams)]
-        lib.ex4d_trainer_set_lr.restype = C.c_int
-        lib.ex4d_trainer_set_lr.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
-        lib.ex4d_trainer_set_sh_degree.restype = C.c_int
-        lib.ex4d_trainer_set_sh_degree.argtypes = [C.c_void_p, C.c_int32]
-        lib.ex4d_trainer_set_async.restype = C.c_int
-        lib.ex4d_trainer_set_async.argtypes = [C.c_void_p, C.c_int32]
-        lib.ex4d_trainer_set_regularizers.restype = C.c_int
-        lib.ex4d_trainer_set_regularizers.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double]
-        lib.ex4d_trainer_replays.restype = C.c_int64
-        lib.ex4d_trainer_replays.argtypes = [C.c_void_p]
-        lib.ex4d_trainer_bytes.restype = C.c_size_t
-        lib.ex4d_trainer_bytes.argtypes = [C.c_void_p]
-        lib._trainer_ready = True
-    return lib
+EXPORTS = _abi.exports("ex4d_trainer.h")
 
 
 class NativeTrainer:
@@ -99,10 +56,10 @@ class NativeTrainer:
         cfg.beta1, cfg.beta2, cfg.eps, cfg.optimizer = betas[0], betas[1], eps, int(bool(optimizer))
         self.cfg = cfg
         lib = _lib()
-        ptrs = (C.c_void_p * 15)(*[p.data_ptr() if p.numel() else None for p in self.params])
+        ptrs = (C.c_void_p * 15)(*[_abi.ptr(p) for p in self.params])
         with torch.cuda.device(dev):
             self.handle = lib.ex4d_trainer_create(C.byref(cfg), ptrs)
-        if not self.handle:
+        if not self.handle:                    # a pointer, not a status: NULL is the refusal
             raise RuntimeError(lib.ex4d_trainer_last_error().decode())
         self.num_rendered = 0
 
@@ -112,14 +69,10 @@ class NativeTrainer:
             raise RuntimeError("camera size differs from the one the trainer was built for")
         if tuple(gt_image.shape) != (3, self.H, self.W) or gt_image.dtype != torch.float32 or not gt_image.is_contiguous() or gt_image.device != self.device:
             raise RuntimeError(f"gt_image must be a contiguous float32 [3,{self.H},{self.W}] tensor on {self.device}")
-        lib = _lib()
         R = C.c_int32(0)
-        with torch.cuda.device(self.device):
-            rc = lib.ex4d_trainer_step(self.handle, float(t), cam.world_view_transform.data_ptr(), cam.full_proj_transform.data_ptr(),
-                                       cam.camera_center.data_ptr(), bg.data_ptr(), gt_image.data_ptr(),
-                                       C.c_void_p(torch.cuda.current_stream().cuda_stream), C.byref(R))
-        if rc:
-            raise RuntimeError(lib.ex4d_trainer_last_error().decode())
+        with _abi.stream(self.device) as stream:
+            _abi.call("ex4d_trainer_step", self.handle, float(t), cam.world_view_transform.data_ptr(), cam.full_proj_transform.data_ptr(),
+                      cam.camera_center.data_ptr(), bg.data_ptr(), gt_image.data_ptr(), stream, C.byref(R))
         self.num_rendered = R.value
         if self.cfg.optimizer:
             torch.autograd.graph.increment_version(self.params)
@@ -129,30 +82,26 @@ class NativeTrainer:
         cur = {n: self.cfg.lr[i] for i, n in enumerate(self.names)}
         cur.update(lrs)
         arr = (C.c_double * 15)(*[float(cur[n]) for n in self.names])
-        if _lib().ex4d_trainer_set_lr(self.handle, arr):
-            raise RuntimeError(_lib().ex4d_trainer_last_error().decode())
+        _abi.call("ex4d_trainer_set_lr", self.handle, arr)
         self.cfg.lr = arr
 
     def set_sh_degree(self, degree):
         """Active SH degree from the next step on (oneupSHdegree, train.py:113-114)."""
-        if _lib().ex4d_trainer_set_sh_degree(self.handle, int(degree)):
-            raise RuntimeError(_lib().ex4d_trainer_last_error().decode())
+        _abi.call("ex4d_trainer_set_sh_degree", self.handle, int(degree))
         self.cfg.sh_degree = int(degree)
         self.model.active_sh_degree = int(degree)
 
     def set_async(self, on=True):
         """Asynchronous rasterizer forward (no instance-count read-back in the middle of the frame; include/ex4d_trainer.h):
         same parameters as the synchronous path -- a frame that overflows its capacity is re-run before the optimizer step."""
-        if _lib().ex4d_trainer_set_async(self.handle, int(bool(on))):
-            raise RuntimeError(_lib().ex4d_trainer_last_error().decode())
+        _abi.call("ex4d_trainer_set_async", self.handle, int(bool(on)))
 
     def set_regularizers(self, static_reg=0.0, motion_reg=0.0, rot_reg=0.0):
         """Weights of the motion regularisers (train.py:155-168) from the next step on, as regularizers.regularizer_weights returns them
         for the iteration (a 3-tuple as the first argument works too); all 0 = off.  output('reg') holds their values."""
         if isinstance(static_reg, (tuple, list)):
             static_reg, motion_reg, rot_reg = static_reg
-        if _lib().ex4d_trainer_set_regularizers(self.handle, float(static_reg), float(motion_reg), float(rot_reg)):
-            raise RuntimeError(_lib().ex4d_trainer_last_error().decode())
+        _abi.call("ex4d_trainer_set_regularizers", self.handle, float(static_reg), float(motion_reg), float(rot_reg))
 
     def replays(self):
         return int(_lib().ex4d_trainer_replays(self.handle))
@@ -179,11 +128,8 @@ class NativeTrainer:
     def _read(self, what, shape, dtype):
         out = torch.empty(shape, dtype=dtype, device=self.device)
         if out.numel():
-            lib = _lib()
-            with torch.cuda.device(self.device):
-                if lib.ex4d_trainer_read(self.handle, what, out.data_ptr(), out.numel() * out.element_size(),
-                                         C.c_void_p(torch.cuda.current_stream().cuda_stream)):
-                    raise RuntimeError(lib.ex4d_trainer_last_error().decode())
+            with _abi.stream(self.device) as stream:
+                _abi.call("ex4d_trainer_read", self.handle, what, out.data_ptr(), out.numel() * out.element_size(), stream)
         return out
 
     def bytes(self):

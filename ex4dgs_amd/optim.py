@@ -11,55 +11,22 @@ import ctypes as C
 
 import torch
 
-from . import _C
+from . import _abi
+from ._abi import Ex4dRadamSlicedRegTensor, Ex4dRadamSlicedTensor, Ex4dRadamTensor
 
-EXPORTS = ("ex4d_optim_last_error", "ex4d_radam_step", "ex4d_radam_step_sliced", "ex4d_radam_step_sliced_reg", "ex4d_radam_sliced_reg_rows")
+EXPORTS = _abi.exports("ex4d_optim.h")
 REG_NONE, REG_MOTION, REG_ROT = 0, 1, 2
-MAX_WINDOWS = 8
+MAX_WINDOWS = _abi.RADAM_MAX_WINDOWS
 MAX_SLICED = 4
 MAX_TENSORS = 32
 
 
-class Ex4dRadamTensor(C.Structure):
-    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
-                ("numel", C.c_int64), ("lr", C.c_double), ("step", C.c_int64), ("nan_to_num", C.c_int32), ("reserved", C.c_int32)]
-
-
-class Ex4dRadamSlicedTensor(C.Structure):
-    _fields_ = [("param", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("rows", C.c_int64), ("K", C.c_int32), ("C", C.c_int32),
-                ("lr", C.c_double), ("step", C.c_int64), ("n_windows", C.c_int32), ("first", C.c_int32 * 8), ("count", C.c_int32 * 8),
-                ("grad", C.c_void_p * 8), ("first_dev", C.c_void_p)]
-
-
-class Ex4dRadamSlicedRegTensor(C.Structure):
-    _fields_ = [("t", Ex4dRadamSlicedTensor), ("reg_kind", C.c_int32), ("reserved", C.c_int32), ("reg_weight", C.c_double), ("reg_rows", C.c_int64)]
-
-
-def _lib():
-    lib = _C.load()
-    if not getattr(lib, "_optim_ready", False):
-        lib.ex4d_radam_step_sliced.restype = C.c_int
-        lib.ex4d_radam_step_sliced.argtypes = [C.POINTER(Ex4dRadamSlicedTensor), C.c_int32, C.c_double, C.c_double, C.c_double, C.c_void_p]
-        lib.ex4d_radam_step_sliced_reg.restype = C.c_int
-        lib.ex4d_radam_step_sliced_reg.argtypes = [C.POINTER(Ex4dRadamSlicedRegTensor), C.c_int32, C.c_double, C.c_double, C.c_double, C.c_void_p]
-        lib.ex4d_radam_sliced_reg_rows.restype = C.c_int32
-        lib.ex4d_radam_sliced_reg_rows.argtypes = [C.c_int32, C.c_int32]
-        lib.ex4d_optim_last_error.restype = C.c_char_p
-        lib.ex4d_radam_step.restype = C.c_int
-        lib.ex4d_radam_step.argtypes = [C.POINTER(Ex4dRadamTensor), C.c_int32, C.c_double, C.c_double, C.c_double, C.c_void_p]
-        lib._optim_ready = True
-    return lib
-
-
 def _launch(descs, struct, entry, limit, betas, eps, device):
     """`entry` over descs (a list of `struct`), at most `limit` per call, on device's current stream; a refused call raises its text."""
-    lib = _lib()
-    with torch.cuda.device(device):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    with _abi.stream(device) as stream:
         for i in range(0, len(descs), limit):
             chunk = descs[i:i + limit]
-            if getattr(lib, entry)((struct * len(chunk))(*chunk), len(chunk), betas[0], betas[1], eps, stream):
-                raise RuntimeError(lib.ex4d_optim_last_error().decode())
+            _abi.call(entry, (struct * len(chunk))(*chunk), len(chunk), betas[0], betas[1], eps, stream)
 
 
 def radam_step_raw(items, betas, eps, device):
@@ -107,7 +74,7 @@ def radam_step_sliced_raw(items, betas, eps, device):
 
 def sliced_reg_rows(K, Cc):
     """Rows of a [rows, K, C] tensor one workgroup of ex4d_radam_step_sliced_reg owns; 0: K is too large for the fused step."""
-    return int(_lib().ex4d_radam_sliced_reg_rows(int(K), int(Cc)))
+    return int(_abi.load().ex4d_radam_sliced_reg_rows(int(K), int(Cc)))
 
 
 def radam_step_sliced_reg_raw(items, betas, eps, device):

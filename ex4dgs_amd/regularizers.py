@@ -9,29 +9,12 @@ trainer.FrameTrainer(regularizers=...) goes further: with sliced keyframe gradie
 optimizer step (optim.radam_step_sliced_reg_raw) and their dense gradient never exists.
 No CPU fallback: everything here needs the HIP library and a ROCm device.
 """
-import ctypes as C
-
 import torch
 
-from . import _C
+from . import _abi
+from ._abi import ptr
 
-EXPORTS = ("ex4d_reg_last_error", "ex4d_reg_scratch_bytes", "ex4d_reg_forward", "ex4d_reg_backward")
-
-
-def _lib():
-    lib = _C.load()
-    if not getattr(lib, "_reg_ready", False):
-        lib.ex4d_reg_last_error.restype = C.c_char_p
-        lib.ex4d_reg_scratch_bytes.restype = C.c_size_t
-        lib.ex4d_reg_scratch_bytes.argtypes = []
-        lib.ex4d_reg_forward.restype = C.c_int
-        lib.ex4d_reg_forward.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_double,
-                                         C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.ex4d_reg_backward.restype = C.c_int
-        lib.ex4d_reg_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
-                                          C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_int32, C.c_void_p]
-        lib._reg_ready = True
-    return lib
+EXPORTS = _abi.exports("ex4d_regularizers.h")
 
 
 def _get(opt, name):
@@ -76,44 +59,34 @@ def _check_inputs(xyz_disp, xyz_motion, rotation_motion):
     return dev, Ns, Nd, K
 
 
-def _ptr(t):
-    return t.data_ptr() if t is not None and t.numel() > 0 else None
-
-
 def forward_raw(xyz_disp, xyz_motion, rotation_motion, weights, out=None, scratch=None):
     """ex4d_reg_forward on the current stream: float32[4] on the device = (static mean, motion mean, rot mean, weighted sum).
     out / scratch: reusable buffers (scratch: new_scratch(device))."""
     dev, Ns, Nd, K = _check_inputs(xyz_disp, xyz_motion, rotation_motion)
-    lib = _lib()
     if out is None:
         out = torch.empty(4, dtype=torch.float32, device=dev)
     if scratch is None:
         scratch = new_scratch(dev)
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        if lib.ex4d_reg_forward(_ptr(xyz_disp), Ns, _ptr(xyz_motion), _ptr(rotation_motion), Nd, K, float(weights[0]), float(weights[1]),
-                                float(weights[2]), out.data_ptr(), scratch.data_ptr(), stream):
-            raise RuntimeError(lib.ex4d_reg_last_error().decode())
+    with _abi.stream(dev) as stream:
+        _abi.call("ex4d_reg_forward", ptr(xyz_disp), Ns, ptr(xyz_motion), ptr(rotation_motion), Nd, K, float(weights[0]), float(weights[1]),
+                  float(weights[2]), out.data_ptr(), scratch.data_ptr(), stream)
     return out
 
 
 def new_scratch(device):
-    return torch.empty(_lib().ex4d_reg_scratch_bytes() // 8, dtype=torch.float64, device=device)
+    return torch.empty(_abi.load().ex4d_reg_scratch_bytes() // 8, dtype=torch.float64, device=device)
 
 
 def backward_raw(xyz_disp, xyz_motion, rotation_motion, weights, grads, upstream=None, accumulate=False):
     """ex4d_reg_backward on the current stream.  grads: (g_xyz_disp, g_xyz_motion, g_rotation_motion), None = skip that tensor;
     upstream: one-element float32 device tensor multiplied into the gradients (None = 1); accumulate: add instead of write."""
     dev, Ns, Nd, K = _check_inputs(xyz_disp, xyz_motion, rotation_motion)
-    lib = _lib()
     for g, p in zip(grads, (xyz_disp, xyz_motion, rotation_motion)):
         if g is not None and (p is None or g.shape != p.shape or g.dtype != torch.float32 or not g.is_contiguous() or g.device != p.device):
             raise RuntimeError("regularizers: a gradient must be contiguous float32 of its parameter's shape, on its device")
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        if lib.ex4d_reg_backward(_ptr(xyz_disp), _ptr(grads[0]), Ns, _ptr(xyz_motion), _ptr(grads[1]), _ptr(rotation_motion), _ptr(grads[2]), Nd, K,
-                                 float(weights[0]), float(weights[1]), float(weights[2]), _ptr(upstream), int(bool(accumulate)), stream):
-            raise RuntimeError(lib.ex4d_reg_last_error().decode())
+    with _abi.stream(dev) as stream:
+        _abi.call("ex4d_reg_backward", ptr(xyz_disp), ptr(grads[0]), Ns, ptr(xyz_motion), ptr(grads[1]), ptr(rotation_motion), ptr(grads[2]), Nd, K,
+                  float(weights[0]), float(weights[1]), float(weights[2]), ptr(upstream), int(bool(accumulate)), stream)
 
 
 class _MotionRegularizers(torch.autograd.Function):

@@ -747,67 +747,6 @@ def test_machine_code_checks_fail_closed(tmp_path, monkeypatch):
         isa_check._llvm_dir()
 
 
-# ------------------------------------------------------------------ C ABI library: builds, loads, exports
-def test_c_abi_library_builds_loads_and_exports_declared_symbols():
-    from ex4dgs_amd import build, _C
-    lib = build.build()
-    assert os.path.exists(lib)
-    hdr = open(os.path.join(h.ROOT, "include", "ex4d_rasterizer.h")).read()
-    body = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    declared = set(re.findall(r"\b(ex4d_[a-z0-9_]+)\s*\(", body)) - {"ex4d_alloc_fn"}
-    assert declared == set(_C.EXPORTS), declared ^ set(_C.EXPORTS)
-    from ex4dgs_amd import attributes
-    hdr2 = re.sub(r"/\*.*?\*/", "", open(os.path.join(h.ROOT, "include", "ex4d_attributes.h")).read(), flags=re.S)
-    declared2 = set(re.findall(r"\b(ex4d_[a-z0-9_]+)\s*\(", hdr2))
-    assert declared2 == set(attributes.EXPORTS), declared2 ^ set(attributes.EXPORTS)
-    assert ctypes.sizeof(attributes.Ex4dAttrParams) == 13 * 4
-    from ex4dgs_amd import loss as loss_mod
-    hdr3 = re.sub(r"/\*.*?\*/", "", open(os.path.join(h.ROOT, "include", "ex4d_loss.h")).read(), flags=re.S)
-    declared3 = set(re.findall(r"\b(ex4d_[a-z0-9_]+)\s*\(", hdr3))
-    assert declared3 == set(loss_mod.EXPORTS), declared3 ^ set(loss_mod.EXPORTS)
-    from ex4dgs_amd import optim as optim_mod
-    hdr4 = re.sub(r"/\*.*?\*/", "", open(os.path.join(h.ROOT, "include", "ex4d_optim.h")).read(), flags=re.S)
-    declared4 = set(re.findall(r"\b(ex4d_[a-z0-9_]+)\s*\(", hdr4))
-    assert declared4 == set(optim_mod.EXPORTS), declared4 ^ set(optim_mod.EXPORTS)
-    assert ctypes.sizeof(optim_mod.Ex4dRadamTensor) == 64
-    from ex4dgs_amd.simple_knn import _C as knn_mod
-    hdr5 = re.sub(r"/\*.*?\*/", "", open(os.path.join(h.ROOT, "include", "ex4d_knn.h")).read(), flags=re.S)
-    declared5 = set(re.findall(r"\b(ex4d_[a-z0-9_]+)\s*\(", hdr5))
-    assert declared5 == set(knn_mod.EXPORTS), declared5 ^ set(knn_mod.EXPORTS)
-    from ex4dgs_amd import native_trainer as nt_mod
-    hdr6 = re.sub(r"/\*.*?\*/", "", open(os.path.join(h.ROOT, "include", "ex4d_trainer.h")).read(), flags=re.S)
-    declared6 = set(re.findall(r"\b(ex4d_[a-z0-9_]+)\s*\(", hdr6))
-    assert declared6 == set(nt_mod.EXPORTS), declared6 ^ set(nt_mod.EXPORTS)
-    assert ctypes.sizeof(nt_mod.Ex4dTrainerConfig) == 280 and nt_mod.Ex4dTrainerConfig.optimizer.offset == 272
-    declared |= declared2 | declared3 | declared4 | declared5 | declared6
-    handle = ctypes.CDLL(lib)
-    for name in declared:
-        assert hasattr(handle, name), name
-    l = _C.load()
-    assert l.ex4d_abi_version() == 5 and l.ex4d_target_arch() == b"gfx950"
-    # size / layout queries are pure host code
-    P = 1000
-    lay = _C.GeomLayout(); l.ex4d_geom_layout(P, ctypes.byref(lay))
-    assert lay.total == l.ex4d_geom_bytes(P) and lay.cov3D >= 64 * P and lay.cov3D % 256 == 0 and lay.records == 0
-    assert l.ex4d_binning_bytes(0, 64, 64) > 0 and l.ex4d_img_bytes(1352, 1014) >= 1352 * 1014 * 8 + 5440 * 8
-    assert l.ex4d_backward_scratch_bytes(P) >= P * 64
-    assert ctypes.sizeof(_C.Ex4dParams) == 17 * 4
-    # library options are host state: the depth sort's default is "auto" (3), values beyond it and unknown names are refused
-    assert _C.get_option("depth_sort_msd") == 3 and _C.get_option("depth_sort_hold") == 0 and _C.get_option("depth_sort_trips") == 0
-    for v in (0, 1, 2, 3):
-        _C.set_option("depth_sort_msd", v)
-        assert _C.get_option("depth_sort_msd") == v
-    with pytest.raises(RuntimeError):
-        _C.set_option("depth_sort_msd", 4)
-    with pytest.raises(RuntimeError):
-        _C.set_option("depth_sort_hold", 1)              # read-only
-    assert _C.get_option("no_such_option") == -1
-    # the kernels are gfx950 code objects
-    out = subprocess.run(["/opt/rocm/lib/llvm/bin/clang-offload-bundler", "--list", "--type=o", f"--input={lib}"], capture_output=True, text=True)
-    if out.returncode == 0 and out.stdout.strip():
-        assert "gfx950" in out.stdout
-
-
 def test_product_path_has_no_cpu_fallback_and_never_imports_the_oracle():
     from ex4dgs_amd.diff_gaussian_rasterization_df import GaussianRasterizer, GaussianRasterizationSettings
     ins, st = _small_scene(P=16, size=32)

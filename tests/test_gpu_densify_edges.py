@@ -382,10 +382,10 @@ def _refused(lib, rc, outputs, what):
 
 
 def test_plan_refuses_bad_arguments_without_writing(hip_lib):
-    from ex4dgs_amd import densify as D
-    lib = D._lib()
+    from ex4dgs_amd import _C, densify as D
+    lib = _C.load()
     n, fill = 8, -7
-    stream = D._stream(DEV)
+    stream = C.c_void_p(torch.cuda.current_stream(DEV).cuda_stream)
     f = lambda *s: torch.zeros(*s, device=DEV)
     stats, scaling, opacity, xyz = f(9, n), f(n, 3), f(n), f(n, 3)
     mp = torch.full((n, 8), fill, dtype=torch.int32, device=DEV)
@@ -409,10 +409,10 @@ def test_plan_refuses_bad_arguments_without_writing(hip_lib):
 
 
 def test_apply_refuses_bad_descriptors_without_writing(hip_lib):
-    from ex4dgs_amd import densify as D
-    lib = D._lib()
+    from ex4dgs_amd import _C, densify as D
+    lib = _C.load()
     n = 8
-    stream = D._stream(DEV)
+    stream = C.c_void_p(torch.cuda.current_stream(DEV).cuda_stream)
     mp = torch.full((n, 8), -1, dtype=torch.int32, device=DEV)
     mp[:, 0] = torch.arange(n, dtype=torch.int32, device=DEV)                       # a valid map: every row kept in place
     z = torch.zeros(64, device=DEV)
