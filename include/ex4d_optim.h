@@ -63,8 +63,11 @@ typedef struct Ex4dRadamSlicedTensor {
     const float *grad[EX4D_RADAM_MAX_WINDOWS];      /* device [rows, count[w], C] */
     const int32_t *first_dev;                       /* optional DEVICE array of n_windows first-keyframe indices: when non-NULL the kernel
                                                        reads the window positions from it and first[] is ignored (windows gathered from
-                                                       other ranks: no device -> host round trip before the launch; a position outside
-                                                       [0, K - count] simply matches no element) */
+                                                       other ranks: no device -> host round trip before the launch).  These positions are
+                                                       not validated: a window that lies partly outside [0, K) counts with the part inside
+                                                       it (keyframe k still takes slice k - first of grad[w], nothing outside the block is
+                                                       read), one that lies wholly outside (first <= -count or first >= K) matches no
+                                                       element */
 } Ex4dRadamSlicedTensor;
 
 int ex4d_radam_step_sliced(const Ex4dRadamSlicedTensor *tensors, int32_t count, double beta1, double beta2, double eps, void *stream);

@@ -524,3 +524,20 @@ def assert_sliced_steps_refuse_bad_descriptors(dev):
     torch.cuda.synchronize()
     for x, x0 in zip((p, m, v), kept):
         assert torch.equal(x, x0)
+
+
+def assert_same_bits(got, ref, may_be_nan, what):
+    """got (device tensor or array) has the bits of ref; NaN where ref is NaN, and ref is NaN only where may_be_nan (None: nowhere)."""
+    got = got.detach().cpu().numpy() if isinstance(got, torch.Tensor) else got
+    got, ref = got.reshape(-1), ref.reshape(-1)
+    assert got.shape == ref.shape and got.dtype == ref.dtype == np.float32, what
+    nan = np.isnan(ref)
+    allowed = np.zeros(ref.shape, bool) if may_be_nan is None else may_be_nan.reshape(-1)
+    assert not (nan & ~allowed).any(), (what, "the restatement is NaN outside the planted elements")
+    assert np.isnan(got[nan]).all(), (what, "NaN expected at", np.flatnonzero(nan & ~np.isnan(got))[:8])
+    a, b = got.view(np.uint32)[~nan], ref.view(np.uint32)[~nan]
+    if not np.array_equal(a, b):
+        bad = np.flatnonzero(~nan)[a != b]
+        i = int(bad[0])
+        raise AssertionError(f"{what}: {bad.size} of {ref.size} elements differ in bits, first at {i}: got {got[i]!r} ({got.view(np.uint32)[i]:#010x}), "
+                             f"expected {ref[i]!r} ({ref.view(np.uint32)[i]:#010x}); indices {bad[:8].tolist()}")

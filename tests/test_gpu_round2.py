@@ -358,28 +358,37 @@ def test_radam_nan_to_num_flag_and_device_side_window_positions(hip_lib):
     _opacity_duration_var.grad before optimizer.step()) -- an injected NaN / inf neither reaches the parameter nor the optimizer state, and
     the result equals torch.optim.RAdam stepped on the sanitised gradient.  (2) Ex4dRadamSlicedTensor.first_dev: window positions read
     from device memory (no host round trip) give the step of the host-side positions bit for bit."""
+    from oracle import optim_oracle
     from ex4dgs_amd.optim import radam_step_raw, radam_step_sliced_raw
     g0 = torch.Generator().manual_seed(4)
     p = torch.randn(5000, generator=g0).cuda()
     ref = torch.nn.Parameter(p.clone())
     opt = torch.optim.RAdam([ref], lr=1e-2)
     m, v = torch.zeros_like(p), torch.zeros_like(p)
+    op, om, ov = p.cpu().numpy().copy(), np.zeros(5000, np.float32), np.zeros(5000, np.float32)
     for step in range(1, 9):
         g = torch.randn(5000, generator=g0).cuda()
         g[17] = float("nan")
         ref.grad = torch.nan_to_num(g)
         opt.step()
         radam_step_raw([(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), 1e-2, step, 1)], (0.9, 0.999), 1e-8, p.device)
+        optim_oracle.radam_step(op, g.cpu().numpy(), om, ov, step, 1e-2, nan_to_num=True)
     torch.cuda.synchronize()
     r = ref.detach()
     assert torch.isfinite(p).all() and torch.isfinite(m).all() and torch.isfinite(v).all()
-    assert float(((p - r).abs() / r.abs().clamp_min(1.0)).max()) <= 2e-6
+    assert float(((p - r).abs() / r.abs().clamp_min(1.0)).max()) <= 2e-6        # torch's own float32 order: a bar; the restatement: bits
+    for got, want, name in ((p, op, "p"), (m, om, "exp_avg"), (v, ov, "exp_avg_sq")):
+        h.assert_same_bits(got, want, None, f"nan_to_num trajectory {name}")
     # +-inf -> +-FLT_MAX (one step: exp_avg = 0.1 x FLT_MAX stays finite, with the sign of the gradient)
     pi, mi, vi = p.clone(), torch.zeros_like(p), torch.zeros_like(p)
     gi = torch.zeros_like(p); gi[99] = float("inf"); gi[100] = float("-inf")
     radam_step_raw([(pi.data_ptr(), gi.data_ptr(), mi.data_ptr(), vi.data_ptr(), pi.numel(), 1e-2, 1, 1)], (0.9, 0.999), 1e-8, p.device)
     torch.cuda.synchronize()
     assert torch.isfinite(mi).all() and float(mi[99]) > 1e37 and float(mi[100]) < -1e37
+    oi, omi, ovi = p.cpu().numpy().copy(), np.zeros(5000, np.float32), np.zeros(5000, np.float32)
+    optim_oracle.radam_step(oi, gi.cpu().numpy(), omi, ovi, 1, 1e-2, nan_to_num=True)
+    for got, want, name in ((pi, oi, "p"), (mi, omi, "exp_avg"), (vi, ovi, "exp_avg_sq")):
+        h.assert_same_bits(got, want, None, f"+-inf -> +-FLT_MAX {name}")
     # without the flag the NaN goes through (the caller asked for the plain step)
     p2, m2, v2 = p.clone(), torch.zeros_like(p), torch.zeros_like(p)
     radam_step_raw([(p2.data_ptr(), g.data_ptr(), m2.data_ptr(), v2.data_ptr(), p2.numel(), 1e-2, 1)], (0.9, 0.999), 1e-8, p.device)
