@@ -97,6 +97,20 @@ class Ex4dDensifyApplyGroup(C.Structure):
                 *_all(f32, "min_len", "center_lo", "center_hi", "split_div")]
 
 
+class Ex4dGrowthClassify(C.Structure):
+    _fields_ = [("n", i64), *_all(vp, "score", "result", "disp", "stats"), ("motion_abs", f32), ("min_abs", f32),
+                *_all(vp, "map", "counts", "selected", "counts_out", "scratch")]
+
+
+class Ex4dGrowthTensor(C.Structure):
+    _fields_ = [*_all(vp, "old", "dst", "src0", "src1"), ("old_rows", i64), ("width", i32), ("rule", i32)]
+
+
+class Ex4dGrowthAppend(C.Structure):
+    _fields_ = [("selected", vp), ("n_new", i64), ("n_static", i64), ("stats", vp), ("K", i32),
+                *_all(f32, "interval", "max_dur", "b_scale", "time_shift", "time_pad", "center_lo", "center_hi")]
+
+
 # ---- ex4d_trainer.h
 class Ex4dTrainerConfig(C.Structure):
     _fields_ = [*_all(i32, "Ns", "Nd", "K", "W", "H", "sh_degree"), *_all(f32, "tanfovx", "tanfovy", "kernel_size", "min_depth", "max_depth"),
@@ -165,7 +179,15 @@ PROTOTYPES = {
         _value("ex4d_densify_scratch_bytes", size, i64),
         _status("ex4d_densify_plan", i32, P(Ex4dDensifyPlanGroup), vp),
         _status("ex4d_densify_apply", P(Ex4dDensifyTensor), i32, P(Ex4dDensifyApplyGroup), vp),
-        _value("ex4d_densify_last_error", text))),
+        _value("ex4d_densify_last_error", text),
+        _status("ex4d_growth_scores", vp, vp, vp, vp, i64, vp, vp),
+        _value("ex4d_growth_select_scratch_bytes", size),
+        _status("ex4d_growth_select", vp, i64, f32, vp, vp, vp),
+        _status("ex4d_growth_classify", P(Ex4dGrowthClassify), vp),
+        _status("ex4d_growth_append", P(Ex4dGrowthTensor), i32, P(Ex4dGrowthAppend), vp),
+        _status("ex4d_growth_extrapolate", vp, vp, i64, i32, i32, i32, i32, vp),
+        _status("ex4d_growth_expand_opacity", vp, vp, vp, vp, i64, f32, f32, f32, vp),
+        _status("ex4d_growth_adjust_opacity", vp, vp, vp, vp, i64, f32, f32, vp))),
     "ex4d_regularizers.h": ("ex4d_reg_last_error", (
         _value("ex4d_reg_last_error", text),
         _value("ex4d_reg_scratch_bytes", size),

@@ -30,6 +30,7 @@ SOURCES = {
     "ex4d_optim.hip": ["-ffp-contract=off"],
     "ex4d_knn.hip": ["-ffp-contract=off"],
     "ex4d_densify.hip": ["-ffp-contract=off"],      # density control: threshold decisions and copied values follow torch's float32 ops
+    "ex4d_growth.hip": ["-ffp-contract=off"],       # growth of the dynamic set (declared in ex4d_densify.h): the same rule
     "ex4d_regularizers.hip": ["-ffp-contract=off"], # motion regularisers: the gradient arithmetic is shared bit for bit with ex4d_optim.hip
     "ex4d_trainer.hip": [],          # host code only: the compiled host path of one training iteration (include/ex4d_trainer.h)
 }

@@ -345,6 +345,13 @@ inline long long num_blocks(long long n) { return (n + DN_THREADS - 1) / DN_THRE
 
 }  // namespace
 
+// the text ex4d_densify_last_error returns, for ex4d_growth.hip (the same header, the same error channel)
+char *ex4d_densify_error_buffer(size_t *capacity)
+{
+    *capacity = sizeof(g_densify_err);
+    return g_densify_err;
+}
+
 extern "C" {
 
 const char *ex4d_densify_last_error(void) { return g_densify_err; }

@@ -130,6 +130,93 @@ int ex4d_densify_apply(const Ex4dDensifyTensor *tensors, int32_t count, const Ex
 
 const char *ex4d_densify_last_error(void);
 
+/* ---- growth of the dynamic set: extract_dynamic_points_from_static (:1147), expand_duration (:1243), adjust_temp_opa (:1330).
+ * Errors of these calls are read with ex4d_densify_last_error as well. */
+
+/* score[i] = |disp_i| / (|xyz_i - cam|^2 + 1e-6) for a visible row, -1 for an invisible one (float32, the reference's op order).
+ * xyz, disp float [n, 3]; vis uint8 [n] (0 = invisible); cam = 3 device floats; score float [n] (written). */
+int ex4d_growth_scores(const float *xyz, const float *disp, const uint8_t *vis, const float *cam, int64_t n, float *score, void *stream);
+
+/* The threshold of torch.quantile(u, q), linear interpolation, over u = s / (max s + 1e-6), s = the entries of `score` without a
+ * sign bit (a NaN counts as present and makes the threshold NaN): a radix select of the two order statistics, no sort.
+ * result (device, written): [EX4D_SELECT_THETA] the threshold, [EX4D_SELECT_MAX] max s, [EX4D_SELECT_COUNT] the number of present
+ * entries as int32 bits, [3] unused.  No present entry: threshold NaN, max 0, count 0. */
+enum { EX4D_SELECT_THETA = 0, EX4D_SELECT_MAX = 1, EX4D_SELECT_COUNT = 2 };
+#define EX4D_SELECT_WORDS 4
+size_t ex4d_growth_select_scratch_bytes(void);
+int ex4d_growth_select(const float *score, int64_t n, float q, float *result, void *scratch, void *stream);
+
+/* Classification of the static rows and its compaction.  Selected: score present and (u > theta or |disp| > motion_abs) and
+ * |disp| > min_abs and error-min timestamp >= 0.  map is written in EX4D_PLAN_MAP_INTS layout (a selected row has no destination)
+ * and counts in EX4D_PLAN_COUNTS layout, so ex4d_densify_apply prunes the static tensors with them; selected[j] is the source row of
+ * the j-th selected row (ascending), counts_out = {selected, kept}. */
+typedef struct Ex4dGrowthClassify {
+    int64_t n;                   /* static rows */
+    const float *score;          /* device [n] from ex4d_growth_scores */
+    const float *result;         /* device [EX4D_SELECT_WORDS] from ex4d_growth_select */
+    const float *disp;           /* device [n, 3] */
+    const float *stats;          /* device [9, n]: the static statistics block */
+    float motion_abs;            /* motion_thres * extent */
+    float min_abs;               /* min_motion_thres * extent */
+    int32_t *map;                /* device [n, EX4D_PLAN_MAP_INTS] (written) */
+    int32_t *counts;             /* device [EX4D_PLAN_COUNTS] (written) */
+    int32_t *selected;           /* device [n] (the first counts_out[0] entries written) */
+    int32_t *counts_out;         /* device [2] (written) */
+    void *scratch;               /* device, ex4d_densify_scratch_bytes(n) */
+} Ex4dGrowthClassify;
+
+int ex4d_growth_classify(const Ex4dGrowthClassify *args, void *stream);
+
+/* The dynamic append: every destination tensor is the old dynamic rows followed by one new row per selected static row. */
+enum {
+    EX4D_GROW_COPY = 0,          /* new row = row of src0 (width floats): features, scaling, opacity */
+    EX4D_GROW_ZERO = 1,          /* new row = 0 (moments) */
+    EX4D_GROW_XYZ = 2,           /* width 3 K: bilinear resize of xyz - disp interval / max_dur and xyz + disp (1 + interval / max_dur) to K samples; src0 = xyz, src1 = disp */
+    EX4D_GROW_ROTATION = 3,      /* width 4 K: the row of src0 [n, 4] repeated K times */
+    EX4D_GROW_CENTER = 4,        /* width 2: the duration centres from the static error-min timestamp */
+    EX4D_GROW_VAR = 5,           /* width 2: (t + time_pad, max_dur - t + time_pad) */
+    EX4D_GROW_STATS = 6          /* a [9, rows] block: rows GRAD_ACCUM .. MIN_RADII reset for every row, ERROR_MIN / ERROR_MIN_T kept for old rows, 1000 / -1 for new ones */
+};
+
+typedef struct Ex4dGrowthTensor {
+    const float *old;            /* device [old_rows, width] ([9, old_rows] for EX4D_GROW_STATS); may be NULL when old_rows == 0 */
+    float *dst;                  /* device [old_rows + n_new, width] (written) */
+    const float *src0, *src1;    /* static sources of the rule */
+    int64_t old_rows;
+    int32_t width;
+    int32_t rule;
+} Ex4dGrowthTensor;
+
+typedef struct Ex4dGrowthAppend {
+    const int32_t *selected;     /* device [n_new] from ex4d_growth_classify */
+    int64_t n_new;
+    int64_t n_static;            /* rows of the static tensors (plane stride of stats) */
+    const float *stats;          /* device [9, n_static] */
+    int32_t K;                   /* keyframes of the new rows */
+    float interval, max_dur;
+    float b_scale;               /* 1 + interval / max_dur */
+    float time_shift, time_pad;
+    float center_lo, center_hi;  /* (time_shift + 1) / interval, (time_shift + max_dur - 1) / interval */
+} Ex4dGrowthAppend;
+
+#define EX4D_GROWTH_MAX_TENSORS 28
+int ex4d_growth_append(const Ex4dGrowthTensor *tensors, int32_t count, const Ex4dGrowthAppend *args, void *stream);
+
+/* expand_duration: dst [rows, K2, C] = the K keyframes of src [rows, K, C] followed by K2 - K extrapolated ones,
+ * dst[K - 1 + j] = j d + src[K - 1], d = the mean over a = 0 .. avg - 1 of src[K - avg + a] - src[K - avg - 1] (summed in
+ * ascending a).  1 <= avg < K < K2. */
+int ex4d_growth_extrapolate(const float *src, float *dst, int64_t rows, int32_t K, int32_t K2, int32_t C, int32_t avg, void *stream);
+
+/* expand_duration's opacity edits.  center / var [rows, 2]: var_out[:, 1] = 1 where either centre + shift > late, else var[:, 1];
+ * var_out[:, 0] = var[:, 0]; center_out = min(center, center_max). */
+int ex4d_growth_expand_opacity(const float *center, const float *var, float *center_out, float *var_out, int64_t rows, float shift,
+                               float late, float center_max, void *stream);
+
+/* adjust_temp_opa: centres clamped to [lo, hi]; var[:, 1] = max(var, 1) 2 where either centre > hi, var[:, 0] likewise where either
+ * centre < lo; then 0.5 wherever the OLD var is < 0.5. */
+int ex4d_growth_adjust_opacity(const float *center, const float *var, float *center_out, float *var_out, int64_t rows, float lo, float hi,
+                               void *stream);
+
 #ifdef __cplusplus
 }
 #endif
