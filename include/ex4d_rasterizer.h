@@ -300,6 +300,7 @@ void ex4d_img_layout(int32_t W, int32_t H, Ex4dImgLayout *out);
  *   "composite_bwd_pairs"    1 (default, round 6) = quadrants with integer pixel positions and no upstream dL_dacc run the compositing backward
  *                            with two pixels per lane on packed math (v_pk_*_f32); 0 = one pixel per lane and step everywhere (rounds 2-5).
  *                            Same decisions, sums reassociated (even / odd columns accumulate apart): equal within the gradient bars.
+ *                            tests/test_gpu_composite_variants.py holds both settings, each of their inner loops, to the oracle.
  *   "readback_side_stream"   1 (default, round 6) = the synchronous forward's one read-back (instance count, frame flags) is copied on a
  *                            stream of the library's own behind an event recorded after the per-Gaussian kernel, so that the depth sort
  *                            does not queue behind the copy and its system-scope release (-14 us per frame at 1.0 M Gaussians);

@@ -83,7 +83,7 @@ def gpu_backward_raw(ins, fwd, grads, device="cuda"):
     s = fwd["settings"]
     e = torch.Tensor([])
     d = lambda k: ins[k].to(device) if ins.get(k) is not None else e
-    gc, gd, gf, ga = [g.to(device) for g in grads]
+    gc, gd, gf, ga = [None if g is None else g.to(device) for g in grads]          # None: a null pointer (absent upstream gradient)
     outs = _C.rasterize_gaussians_backward(
         s.bg, d("means3D"), fwd["radii"], d("colors_precomp"), d("scales"), d("rotations"), fwd["depth"], fwd["acc"], s.min_depth,
         s.max_depth, s.scale_modifier, d("cov3D_precomp"), s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, s.kernel_size,

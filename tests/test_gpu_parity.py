@@ -19,9 +19,12 @@ _ORACLE_FWD = {}       # (cfg, P, t, degree) -> oracle forward of the unmodified
                        # options and once with the library's defaults (the timed configuration) against the same oracle result
 
 
-def _fwd_bwd(cfg, P=None, t=0, sh_degree=3, grad_acc_zero=False, mutate=None, subpixel=None, seed=3, max_fragile_frac=2e-3, noise_orders=8, dir_scale=0.1, **fwd_over):
+def _fwd_bwd(cfg, P=None, t=0, sh_degree=3, grad_acc_zero=False, mutate=None, subpixel=None, seed=3, max_fragile_frac=2e-3, noise_orders=8, dir_scale=0.1, grads=None, **fwd_over):
     """dir_scale = 0: every dir3D is zero, the caller's case (gaussian_renderer/__init__.py:66-70 passes the zero gradient trap) and
-    the one bench.py times -- the flow-free forward kernel with the hand-scheduled entry walk is launched; any other value exercises the kernel with flow."""
+    the one bench.py times -- the flow-free forward kernel with the hand-scheduled entry walk is launched; any other value exercises the kernel with flow.
+    grads: optional callable(oracle forward) -> the four upstream gradients [colour, depth, flow, acc] (default: scene.upstream_grads); any of
+    the last three may be None -- the HIP backward then gets a null pointer, the oracle zeros.  What was passed on, after the
+    fragile-pixel mask, comes back as rep["upstream"]."""
     from oracle import oracle
     ins, st = h.scene_inputs(cfg, P=P, t=t, sh_degree=sh_degree, dir_scale=dir_scale)
     st.update(fwd_over)
@@ -38,9 +41,10 @@ def _fwd_bwd(cfg, P=None, t=0, sh_degree=3, grad_acc_zero=False, mutate=None, su
     g = h.gpu_forward_raw(ins, st, subpixel_offset=subpixel)
     rep = h.compare_forward(o, g, max_fragile_frac=max_fragile_frac, tag=f"{cfg if isinstance(cfg, str) else cfg.name} P={o['P']} t={t}")
     H, W = st["image_height"], st["image_width"]
-    grads = list(h.upstream_grads(torch.from_numpy(o["acc"]), H, W, seed=seed, grad_acc_zero=grad_acc_zero))
+    grads = list(h.upstream_grads(torch.from_numpy(o["acc"]), H, W, seed=seed, grad_acc_zero=grad_acc_zero) if grads is None else grads(o))
     solid = torch.from_numpy(o["fragile"] > h.FRAG_EPS)
-    grads = [x * solid[None] for x in grads]          # a flipped pair changes the whole pixel: exclude fragile pixels
+    passed = [None if x is None else x * solid[None] for x in grads]          # a flipped pair changes the whole pixel: exclude fragile pixels
+    grads = [torch.zeros(n, H, W) if x is None else x for x, n in zip(passed, (3, 1, 3, 1))]      # (the oracle's: absent = zeros)
     # The backward consumes the forward's per-pixel state (out_depth, out_acc, final_T, n_contrib).  dL_dalpha contains
     # (final_depth - depth) * dL_ddepth, a difference of nearly equal depths, so a 1e-6 relative difference in out_depth
     # (forward rounding, already checked above) would be amplified ~1e2-1e3x into the gradients.  To test the BACKWARD
@@ -52,7 +56,7 @@ def _fwd_bwd(cfg, P=None, t=0, sh_degree=3, grad_acc_zero=False, mutate=None, su
     # the reference's own noise floor: the same backward replayed in float32 with the pixels in `noise_orders` random orders
     # (its atomicAdd order changes from run to run, CR/backward.cu:613-679); the HIP error is asserted in multiples of that spread
     noise = oracle.backward_noise(ob_state, *grads, orders=noise_orders) if noise_orders else None
-    gb = h.gpu_backward_raw(ins, g, grads)
+    gb = h.gpu_backward_raw(ins, g, passed)
     rep.update(h.compare_backward(ob, gb, o, noise=noise, tag=f"{cfg if isinstance(cfg, str) else cfg.name} P={o['P']} t={t} (oracle backward on the GPU forward's state)"))
     # end to end: oracle(forward -> backward) against GPU(forward -> backward), nothing shared but the inputs.  The oracle's own
     # forward state differs from the GPU's by forward rounding (<= 1e-5, checked above), which the backward amplifies where a term is
@@ -71,6 +75,7 @@ def _fwd_bwd(cfg, P=None, t=0, sh_degree=3, grad_acc_zero=False, mutate=None, su
     rep["e2e"] = h.compare_backward(ob_e2e, gb, o, extra13=2.0 * ob_e2e["state13"], tag=f"{cfg if isinstance(cfg, str) else cfg.name} P={o['P']} t={t} END-TO-END")
     # per-Gaussian backward stage in isolation: feed the GPU's own accumulators to the oracle's stage
     h.assert_per_gaussian_stage_bit_exact(o, gb, ob)
+    rep["upstream"] = passed
     return o, g, ob, gb, rep
 
 
