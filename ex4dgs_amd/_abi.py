@@ -118,6 +118,14 @@ class Ex4dTrainerConfig(C.Structure):
                 ("lr", f64 * TRAINER_PARAMS), *_all(f64, "beta1", "beta2", "eps"), ("optimizer", i32)]
 
 
+class Ex4dTrainerStepOptions(C.Structure):
+    _fields_ = [*_all(i32, "l1_accum", "skip_optimizer", "stats_flags", "nan_census"), *_all(vp, "stats_s", "stats_d")]
+
+
+class Ex4dTrainerReport(C.Structure):
+    _fields_ = [("loss", f32), *_all(i32, "nan_static", "nan_dynamic", "reserved")]
+
+
 def _status(name, *argtypes):
     """An entry point whose int return is a status: 0, or an error whose text the header's *_last_error holds (see call)."""
     return name, cint, argtypes, True
@@ -176,6 +184,7 @@ PROTOTYPES = {
         _status("ex4d_dist2", i32, vp, vp, vp, vp))),
     "ex4d_densify.h": ("ex4d_densify_last_error", (
         _status("ex4d_densify_stats", vp, i64, vp, i64, vp, vp, vp, f32, i32, vp),
+        _status("ex4d_nan_any", vp, i64, vp, i64, vp, vp),
         _value("ex4d_densify_scratch_bytes", size, i64),
         _status("ex4d_densify_plan", i32, P(Ex4dDensifyPlanGroup), vp),
         _status("ex4d_densify_apply", P(Ex4dDensifyTensor), i32, P(Ex4dDensifyApplyGroup), vp),
@@ -199,6 +208,8 @@ PROTOTYPES = {
         _value("ex4d_trainer_destroy", None, vp),
         _value("ex4d_trainer_time_scalars", None, P(Ex4dTrainerConfig), f64, P(Ex4dAttrParams)),
         _status("ex4d_trainer_step", vp, f64, *[vp] * 6, P(i32)),
+        _status("ex4d_trainer_step_ex", vp, f64, *[vp] * 6, P(i32), P(Ex4dTrainerStepOptions)),
+        _status("ex4d_trainer_report", vp, P(Ex4dTrainerReport)),
         _status("ex4d_trainer_set_lr", vp, P(f64)),
         _status("ex4d_trainer_set_sh_degree", vp, i32),
         _status("ex4d_trainer_set_async", vp, i32),
@@ -207,6 +218,9 @@ PROTOTYPES = {
         _value("ex4d_trainer_output", vp, vp, i32),
         _value("ex4d_trainer_grad", vp, vp, i32, P(i32)),
         _status("ex4d_trainer_read", vp, i32, vp, size, vp),
+        _status("ex4d_trainer_write", vp, i32, vp, size, vp),
+        _status("ex4d_trainer_get_step", vp, P(i64)),
+        _status("ex4d_trainer_set_step", vp, i64),
         _value("ex4d_trainer_bytes", size, vp))),
 }
 # status function -> the *_last_error of its header

@@ -56,6 +56,56 @@ __global__ __launch_bounds__(DN_THREADS) void densify_stats_kernel(float *__rest
     st[EX4D_STAT_ERROR_DENOM * n + i] = st[EX4D_STAT_ERROR_DENOM * n + i] + (e0 > 0.f ? 1.f : 0.f);
 }
 
+// ---------------------------------------------------------------------------------------------------------------- NaN census
+#define DN_NAN_UNROLL 4                     // 16-byte loads in flight per thread and trip
+#define DN_NAN_MAX_BLOCKS 2048              // per array: enough waves to saturate the memory system, the rest is the grid-stride loop
+
+__global__ void nan_flags_clear_kernel(int *__restrict__ flags2)
+{
+    if (threadIdx.x < 2) flags2[threadIdx.x] = 0;
+}
+
+// (bitwise, not short-circuit: every word of a 16-byte load is looked at, so the load stays one instruction)
+__device__ __forceinline__ bool nan_bits(unsigned u) { return (u & 0x7fffffffu) > 0x7f800000u; }
+__device__ __forceinline__ bool nan_bits4(const uint4 &v) { return nan_bits(v.x) | nan_bits(v.y) | nan_bits(v.z) | nan_bits(v.w); }
+
+// Blocks [0, blocks_a) stream a, the others b.  An array is a scalar head up to the first 16-byte boundary (at most 3 floats), an
+// aligned body of uint4 loads and a scalar tail (at most 3 floats); head and tail belong to the array's first block.  Every thread
+// reaches the ballot; a wave that saw a NaN stores 1 -- all writers store the same value, so there is nothing to order.
+__global__ __launch_bounds__(DN_THREADS) void nan_any_kernel(const float *__restrict__ a, long long n_a, const float *__restrict__ b, long long n_b,
+                                                              unsigned blocks_a, int *__restrict__ flags2)
+{
+    const bool second = blockIdx.x >= blocks_a;
+    const float *p = second ? b : a;
+    const long long n = second ? n_b : n_a;
+    const unsigned blk = second ? blockIdx.x - blocks_a : blockIdx.x;
+    const unsigned nblk = second ? gridDim.x - blocks_a : blocks_a;
+    long long head = (long long)(((16u - (unsigned)((uintptr_t)p & 15u)) & 15u) >> 2);
+    if (head > n) head = n;
+    const long long n16 = (n - head) >> 2;
+    const long long tail0 = head + 4 * n16;
+    const uint4 *__restrict__ body = reinterpret_cast<const uint4 *>(p + head);
+    bool found = false;
+    const long long stride = (long long)nblk * DN_THREADS;
+    long long i = (long long)blk * DN_THREADS + threadIdx.x;
+    for (; i + (DN_NAN_UNROLL - 1) * stride < n16; i += DN_NAN_UNROLL * stride) {
+        uint4 v[DN_NAN_UNROLL];
+#pragma unroll
+        for (int k = 0; k < DN_NAN_UNROLL; k++) v[k] = body[i + k * stride];
+#pragma unroll
+        for (int k = 0; k < DN_NAN_UNROLL; k++) found |= nan_bits4(v[k]);
+    }
+    for (; i < n16; i += stride) {
+        found |= nan_bits4(body[i]);
+    }
+    if (blk == 0) {
+        const long long t = threadIdx.x;
+        if (t < head) found |= nan_bits(__float_as_uint(p[t]));
+        if (tail0 + t < n) found |= nan_bits(__float_as_uint(p[tail0 + t]));
+    }
+    if (__ballot(found) != 0ull && (threadIdx.x & 63) == 0) flags2[second ? 1 : 0] = 1;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- plan
 __device__ __forceinline__ float max3(float a, float b, float c)
 {
@@ -447,6 +497,28 @@ int ex4d_densify_apply(const Ex4dDensifyTensor *tensors, int32_t count, const Ex
     if (chunks == 0) return EX4D_OK;
     hipLaunchKernelGGL(densify_apply_kernel, dim3(chunks), dim3(DN_THREADS), 0, (hipStream_t)stream_, a);
     return launch_error("densify_apply");
+}
+
+int ex4d_nan_any(const float *a, int64_t n_a, const float *b, int64_t n_b, int32_t *flags2, void *stream_)
+{
+    g_densify_err[0] = 0;
+    if (!flags2 || n_a < 0 || n_b < 0 || (n_a > 0 && !a) || (n_b > 0 && !b) || (((uintptr_t)a | (uintptr_t)b | (uintptr_t)flags2) & 3u)) {
+        snprintf(g_densify_err, sizeof(g_densify_err), "nan_any: null flags, negative size, null or misaligned array");
+        return EX4D_ERR_ARG;
+    }
+    hipStream_t stream = (hipStream_t)stream_;
+    hipLaunchKernelGGL(nan_flags_clear_kernel, dim3(1), dim3(64), 0, stream, (int *)flags2);
+    unsigned blocks[2];
+    const int64_t n[2] = { n_a, n_b };
+    for (int k = 0; k < 2; k++) {
+        // one block per DN_THREADS * DN_NAN_UNROLL 16-byte loads, at least one for a non-empty array (its head / tail)
+        const long long per = (long long)DN_THREADS * DN_NAN_UNROLL * 4;
+        const long long want = (n[k] + per - 1) / per;
+        blocks[k] = n[k] == 0 ? 0u : (unsigned)(want > DN_NAN_MAX_BLOCKS ? DN_NAN_MAX_BLOCKS : want);
+    }
+    if (blocks[0] + blocks[1] > 0)
+        hipLaunchKernelGGL(nan_any_kernel, dim3(blocks[0] + blocks[1]), dim3(DN_THREADS), 0, stream, a, (long long)n_a, b, (long long)n_b, blocks[0], (int *)flags2);
+    return launch_error("nan_any");
 }
 
 }  // extern "C"

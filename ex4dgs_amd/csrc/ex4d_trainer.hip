@@ -9,6 +9,7 @@
 #include <new>
 
 #include "../../include/ex4d_attributes.h"
+#include "../../include/ex4d_densify.h"
 #include "../../include/ex4d_loss.h"
 #include "../../include/ex4d_optim.h"
 #include "../../include/ex4d_rasterizer.h"
@@ -87,6 +88,15 @@ struct Ex4dTrainer {
     double reg_w[3] = { 0.0, 0.0, 0.0 };
     float *reg_out = nullptr;
     double *reg_scratch = nullptr;
+    // the l1_accum hook [3,H,W] (train.py:148-153): plane 0 IS the accumulation image (`acc` points at it: the rasterizer forward writes
+    // it in place), planes 1 and 2 receive l1_errors / ssim_errors from the loss forward of an l1_accum step
+    float *hook = nullptr;
+    // the report of ex4d_trainer_step_ex: the loss word and the two census flags are neighbours on the device ({loss, nan_static,
+    // nan_dynamic, unused}: `loss` points at word 0), so one 16-byte copy brings them to pinned host memory behind report_ev
+    int32_t *report_dev = nullptr;
+    Ex4dTrainerReport *report = nullptr;
+    hipEvent_t report_ev = nullptr;
+    bool report_pending = false, report_census = false;
     void *owned[96] = {};
     int n_owned = 0;
 
@@ -118,6 +128,8 @@ void ex4d_trainer_destroy(Ex4dTrainer *t)
     if (t->img.ptr) (void)hipFree(t->img.ptr);
     if (t->status) (void)hipHostFree(t->status);
     if (t->status_ev) (void)hipEventDestroy(t->status_ev);
+    if (t->report) (void)hipHostFree(t->report);
+    if (t->report_ev) (void)hipEventDestroy(t->report_ev);
     delete t;
 }
 
@@ -149,8 +161,8 @@ Ex4dTrainer *ex4d_trainer_create(const Ex4dTrainerConfig *cfg, float *const *par
     }
     const size_t P = (size_t)t->P, HW = t->HW;
     ok = ok && t->take(t->means3D, 3 * P) && t->take(t->rotations, 4 * P) && t->take(t->opacities, P) && t->take(t->scales, 3 * P)
-            && t->take(t->color, 3 * HW) && t->take(t->depth, HW) && t->take(t->acc, HW) && t->take(t->flow, 3 * HW) && t->take(t->idx, HW)
-            && t->take(t->radii, P) && t->take(t->loss, 1) && t->take(t->dmaps, 9 * HW)
+            && t->take(t->color, 3 * HW) && t->take(t->depth, HW) && t->take(t->hook, 3 * HW) && t->take(t->flow, 3 * HW) && t->take(t->idx, HW)
+            && t->take(t->radii, P) && t->take(t->report_dev, 4, true) && t->take(t->dmaps, 9 * HW)
             && t->take(t->loss_scratch, ex4d_l1_ssim_scratch_floats(cfg->H, cfg->W)) && t->take(t->grad_img, 3 * HW) && t->take(t->grad_loss, 1)
             && t->take(t->g_means2D, 3 * P) && t->take(t->g_opacity, P) && t->take(t->g_means3D, 3 * P)
             && t->take(t->g_scales, 3 * P) && t->take(t->g_rotations, 4 * P) && t->take(t->g_dir, 3 * P);
@@ -159,6 +171,8 @@ Ex4dTrainer *ex4d_trainer_create(const Ex4dTrainerConfig *cfg, float *const *par
         ok = t->take(reinterpret_cast<unsigned char *&>(s), ex4d_backward_scratch_bytes(t->P));
         t->bwd_scratch = s;
     }
+    t->acc = t->hook;
+    t->loss = reinterpret_cast<float *>(t->report_dev);
     ok = ok && t->take(t->reg_out, 4, true) && t->take(t->reg_scratch, ex4d_reg_scratch_bytes() / sizeof(double));
     if (ok) {
         const float one = 1.0f;
@@ -205,9 +219,30 @@ void ex4d_trainer_time_scalars(const Ex4dTrainerConfig *cfg, double timestamp, E
 int ex4d_trainer_step(Ex4dTrainer *t, double timestamp, const float *viewmatrix, const float *projmatrix, const float *campos,
                       const float *background, const float *gt_image, void *stream, int32_t *num_rendered)
 {
+    return ex4d_trainer_step_ex(t, timestamp, viewmatrix, projmatrix, campos, background, gt_image, stream, num_rendered, nullptr);
+}
+
+int ex4d_trainer_step_ex(Ex4dTrainer *t, double timestamp, const float *viewmatrix, const float *projmatrix, const float *campos,
+                         const float *background, const float *gt_image, void *stream, int32_t *num_rendered,
+                         const Ex4dTrainerStepOptions *opt)
+{
     t_err[0] = 0;
     if (!t || !viewmatrix || !projmatrix || !campos || !background || !gt_image) return tfail(EX4D_ERR_ARG, "null argument");
     const Ex4dTrainerConfig &c = t->cfg;
+    const bool l1_accum = opt && opt->l1_accum, skip_optimizer = opt && opt->skip_optimizer, census = opt && opt->nan_census;
+    const int32_t stats_flags = opt ? opt->stats_flags : 0;
+    const int32_t error_stats = EX4D_DENSIFY_PRUNE_STATS | EX4D_DENSIFY_L1_STATS;
+    if (stats_flags & ~(EX4D_DENSIFY_GRAD_STATS | error_stats)) return tfail(EX4D_ERR_ARG, "unknown statistics flags 0x%x", (unsigned)stats_flags);
+    if ((stats_flags & error_stats) && !l1_accum)
+        return tfail(EX4D_ERR_ARG, "PRUNE_STATS / L1_STATS read the error gradient: the step needs l1_accum");
+    if (stats_flags && ((c.Ns > 0 && !opt->stats_s) || (c.Nd > 0 && !opt->stats_d))) return tfail(EX4D_ERR_ARG, "statistics asked for without their blocks");
+    if (opt && !t->report) {
+        if (hipHostMalloc((void **)&t->report, sizeof(Ex4dTrainerReport), hipHostMallocDefault) != hipSuccess) { t->report = nullptr; return tfail(EX4D_ERR_HIP, "pinned report allocation failed"); }
+        memset(t->report, 0, sizeof(Ex4dTrainerReport));
+        if (hipEventCreateWithFlags(&t->report_ev, hipEventDisableTiming) != hipSuccess) { t->report_ev = nullptr; return tfail(EX4D_ERR_HIP, "event creation failed"); }
+    }
+    float *const l1_errors = l1_accum ? t->hook + t->HW : nullptr, *const ssim_errors = l1_accum ? t->hook + 2 * t->HW : nullptr;
+    const float *const dL_dout_flow = l1_accum ? t->hook : nullptr;
     Ex4dAttrParams a;
     ex4d_trainer_time_scalars(&c, timestamp, &a);
     float *const *p = t->param;
@@ -245,13 +280,13 @@ int ex4d_trainer_step(Ex4dTrainer *t, double timestamp, const float *viewmatrix,
             R = (int32_t)t->capacity;                        // the backward lays the buffers out for the capacity
         }
 
-        if (ex4d_l1_ssim_forward(3, c.H, c.W, t->color, gt_image, c.lambda_dssim, c.window, t->loss, nullptr, nullptr, t->dmaps, t->loss_scratch, stream))
+        if (ex4d_l1_ssim_forward(3, c.H, c.W, t->color, gt_image, c.lambda_dssim, c.window, t->loss, l1_errors, ssim_errors, t->dmaps, t->loss_scratch, stream))
             return tfail(EX4D_ERR_HIP, "loss forward: %s", ex4d_loss_last_error());
         if (ex4d_l1_ssim_backward(3, c.H, c.W, t->color, gt_image, c.lambda_dssim, c.window, t->dmaps, t->grad_loss, t->grad_img, stream))
             return tfail(EX4D_ERR_HIP, "loss backward: %s", ex4d_loss_last_error());
 
         rc = ex4d_backward_split_sh(&prm, R, background, t->means3D, t->radii, &sh, t->scales, t->rotations, nullptr, viewmatrix, projmatrix, campos,
-                                    nullptr, t->depth, t->acc, t->geom.ptr, t->binning.ptr, t->img.ptr, t->grad_img, nullptr, nullptr, nullptr,
+                                    nullptr, t->depth, t->acc, t->geom.ptr, t->binning.ptr, t->img.ptr, t->grad_img, nullptr, dL_dout_flow, nullptr,
                                     t->g_means2D, nullptr, t->g_opacity, t->g_means3D, nullptr, &gsh, t->g_scales, t->g_rotations, t->g_dir,
                                     t->bwd_scratch, stream);
         if (rc) return tfail(rc, "rasterizer backward: %s", ex4d_last_error());
@@ -276,7 +311,14 @@ int ex4d_trainer_step(Ex4dTrainer *t, double timestamp, const float *viewmatrix,
         t->replays++;
     }
 
-    const bool reg = t->reg_w[0] != 0.0 || t->reg_w[1] != 0.0 || t->reg_w[2] != 0.0;
+    // train.py:199-216 on the frame that counts: a frame re-run after an overflow has left the loop exactly once
+    if (stats_flags) {
+        const int rc = ex4d_densify_stats(opt->stats_s, c.Ns, opt->stats_d, c.Nd, t->radii, t->g_means2D, l1_accum ? t->g_dir : nullptr,
+                                          (float)timestamp, stats_flags, stream);
+        if (rc) return tfail(rc, "statistics: %s", ex4d_densify_last_error());
+    }
+
+    const bool reg = !skip_optimizer && (t->reg_w[0] != 0.0 || t->reg_w[1] != 0.0 || t->reg_w[2] != 0.0);
     if (reg) {
         // train.py:155-168: the three terms at this iteration's parameters; the L1/SSIM loss stays in loss[1]
         if (ex4d_reg_forward(p[XYZ_DISP], c.Ns, p[XYZ_MOTION], p[ROTATION_MOTION], c.Nd, c.K, t->reg_w[0], t->reg_w[1], t->reg_w[2], t->reg_out, t->reg_scratch, stream))
@@ -285,7 +327,7 @@ int ex4d_trainer_step(Ex4dTrainer *t, double timestamp, const float *viewmatrix,
         if (c.optimizer && ex4d_reg_backward(p[XYZ_DISP], g[XYZ_DISP], c.Ns, nullptr, nullptr, nullptr, nullptr, 0, 1, t->reg_w[0], 0.0, 0.0, nullptr, 1, stream))
             return tfail(EX4D_ERR_HIP, "regularisers: %s", ex4d_reg_last_error());
     }
-    if (c.optimizer) {
+    if (c.optimizer && !skip_optimizer) {
         t->step += 1;
         Ex4dRadamTensor dense[EX4D_TRAINER_PARAMS];
         Ex4dRadamSlicedRegTensor slr[2];
@@ -317,6 +359,28 @@ int ex4d_trainer_step(Ex4dTrainer *t, double timestamp, const float *viewmatrix,
             if (ex4d_radam_step_sliced(sl, ns, c.beta1, c.beta2, c.eps, stream)) return tfail(EX4D_ERR_HIP, "RAdam (sliced): %s", ex4d_optim_last_error());
         }
     }
+    if (opt) {
+        // train.py:253 (prune_nan_points' gate, c_gaussian_model.py:1230, :1234) at the parameters the optimizer step just left
+        const int rc = census ? ex4d_nan_any(p[XYZ], t->numel[XYZ], p[XYZ_MOTION], t->numel[XYZ_MOTION], t->report_dev + 1, stream) : EX4D_OK;
+        if (rc) return tfail(rc, "NaN census: %s", ex4d_densify_last_error());
+        if (hipMemcpyAsync(t->report, t->report_dev, sizeof(Ex4dTrainerReport), hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess
+            || hipEventRecord(t->report_ev, (hipStream_t)stream) != hipSuccess)
+            return tfail(EX4D_ERR_HIP, "report copy failed: %s", hipGetErrorString(hipGetLastError()));
+        t->report_pending = true;
+        t->report_census = census;
+    }
+    return EX4D_OK;
+}
+
+int ex4d_trainer_report(Ex4dTrainer *t, Ex4dTrainerReport *out)
+{
+    t_err[0] = 0;
+    if (!t || !out) return tfail(EX4D_ERR_ARG, "null argument");
+    if (!t->report_pending) return tfail(EX4D_ERR_ARG, "no step with options has run: nothing to report");
+    if (hipEventSynchronize(t->report_ev) != hipSuccess) return tfail(EX4D_ERR_HIP, "event wait failed");
+    *out = *t->report;
+    if (!t->report_census) out->nan_static = out->nan_dynamic = 0;      // flags of an earlier census are not this step's
+    out->reserved = 0;
     return EX4D_OK;
 }
 
@@ -377,6 +441,8 @@ const void *ex4d_trainer_output(const Ex4dTrainer *t, int32_t what)
     case 4: return t->depth;
     case 5: return t->acc;
     case 6: return t->reg_out;
+    case 7: return t->g_dir;
+    case 8: return t->hook;
     default: return nullptr;
     }
 }
@@ -396,15 +462,49 @@ int ex4d_trainer_read(const Ex4dTrainer *t, int32_t what, void *dst, size_t byte
     size_t have = 0;
     const size_t P = (size_t)t->P, HW = t->HW;
     if (what >= 100 && what < 100 + EX4D_TRAINER_PARAMS) { src = t->grad[what - 100]; have = (size_t)t->grad_numel[what - 100] * sizeof(float); }
+    else if (what >= 200 && what < 200 + EX4D_TRAINER_PARAMS) { src = t->m[what - 200]; have = t->cfg.optimizer ? (size_t)t->numel[what - 200] * sizeof(float) : 0; }
+    else if (what >= 300 && what < 300 + EX4D_TRAINER_PARAMS) { src = t->v[what - 300]; have = t->cfg.optimizer ? (size_t)t->numel[what - 300] * sizeof(float) : 0; }
     else {
         src = ex4d_trainer_output(t, what);
-        const size_t sizes[7] = { sizeof(float), 3 * HW * sizeof(float), P * sizeof(int32_t), 3 * P * sizeof(float), HW * sizeof(float), HW * sizeof(float),
-                                  4 * sizeof(float) };
-        if (what >= 0 && what < 7) have = sizes[what];
+        const size_t sizes[9] = { sizeof(float), 3 * HW * sizeof(float), P * sizeof(int32_t), 3 * P * sizeof(float), HW * sizeof(float), HW * sizeof(float),
+                                  4 * sizeof(float), 3 * P * sizeof(float), 3 * HW * sizeof(float) };
+        if (what >= 0 && what < 9) have = sizes[what];
     }
     if (bytes > have || (bytes > 0 && !src)) return tfail(EX4D_ERR_ARG, "buffer %d holds %zu bytes, %zu requested", what, have, bytes);
     if (bytes && hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess)
         return tfail(EX4D_ERR_HIP, "device copy failed: %s", hipGetErrorString(hipGetLastError()));
+    return EX4D_OK;
+}
+
+int ex4d_trainer_write(Ex4dTrainer *t, int32_t what, const void *src, size_t bytes, void *stream)
+{
+    t_err[0] = 0;
+    if (!t || !src) return tfail(EX4D_ERR_ARG, "null argument");
+    void *dst = nullptr;
+    size_t have = 0;
+    if (what >= 200 && what < 200 + EX4D_TRAINER_PARAMS) { dst = t->m[what - 200]; have = (size_t)t->numel[what - 200] * sizeof(float); }
+    else if (what >= 300 && what < 300 + EX4D_TRAINER_PARAMS) { dst = t->v[what - 300]; have = (size_t)t->numel[what - 300] * sizeof(float); }
+    else return tfail(EX4D_ERR_ARG, "buffer %d cannot be written: only the optimizer state (200 + i, 300 + i) can", what);
+    if (!t->cfg.optimizer) return tfail(EX4D_ERR_ARG, "the trainer was built without an optimizer: it has no state to write");
+    if (bytes > have || (bytes > 0 && !dst)) return tfail(EX4D_ERR_ARG, "buffer %d holds %zu bytes, %zu given", what, have, bytes);
+    if (bytes && hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess)
+        return tfail(EX4D_ERR_HIP, "device copy failed: %s", hipGetErrorString(hipGetLastError()));
+    return EX4D_OK;
+}
+
+int ex4d_trainer_get_step(const Ex4dTrainer *t, int64_t *step)
+{
+    t_err[0] = 0;
+    if (!t || !step) return tfail(EX4D_ERR_ARG, "null argument");
+    *step = t->step;
+    return EX4D_OK;
+}
+
+int ex4d_trainer_set_step(Ex4dTrainer *t, int64_t step)
+{
+    t_err[0] = 0;
+    if (!t || step < 0) return tfail(EX4D_ERR_ARG, "null trainer or negative step count");
+    t->step = step;
     return EX4D_OK;
 }
 

@@ -8,7 +8,9 @@ on the HIP library, with the matching edits of the optimizer state.
 
 `opt` is a torch.optim.Optimizer over the reference's 15 groups (FusedRAdam or torch.optim.RAdam: state re-keyed to the new
 parameter objects, `step` kept, moments gathered / zero for new rows), a trainer.FrameTrainer (m / v remapped, its buffers rebuilt,
-the pending gradients dropped -- train.py densifies before optimizer.step(), whose replaced parameters have no .grad), or None.
+the pending gradients dropped -- train.py densifies before optimizer.step(), whose replaced parameters have no .grad), a
+native_trainer.NativeTrainer (its moments read out, a new native handle over the new tensors, moments and step count written back; run
+the step before it with apply_optimizer=False), or None.
 Random draws are inputs: by default torch.randn on the device (optionally from `generator`), in the reference's draw order; `noise`
 hands in explicit draws.  No CPU fallback: everything runs on a ROCm device.
 """
@@ -97,9 +99,13 @@ class DensityStats:
 # ---------------------------------------------------------------------------------------------------- optimizer adapters
 def _opt_state(opt, params):
     """{name: (exp_avg, exp_avg_sq) or None} of the optimizer for the current parameter objects."""
+    from .native_trainer import NativeTrainer
     from .trainer import FrameTrainer
     if opt is None:
         return {n: None for n in params}
+    if isinstance(opt, NativeTrainer):
+        state = opt._moments if opt._moments is not None else opt.begin_density_control()
+        return {n: state[n] for n in params}
     if isinstance(opt, FrameTrainer):
         if not getattr(opt, "optimizer", False) or not hasattr(opt, "m"):
             return {n: None for n in params}
@@ -113,6 +119,7 @@ def _opt_state(opt, params):
 
 
 def _rebind(model, opt, new_params, new_moments):
+    from .native_trainer import NativeTrainer
     from .trainer import FrameTrainer
     old = {n: getattr(model, n) for n in new_params}
     fresh = {}
@@ -125,7 +132,7 @@ def _rebind(model, opt, new_params, new_moments):
         model._drop_fused_cache()
     if opt is None:
         return
-    if isinstance(opt, FrameTrainer):
+    if isinstance(opt, (FrameTrainer, NativeTrainer)):
         opt.rebind_parameters(new_moments)
         return
     for group in opt.param_groups:
@@ -142,8 +149,9 @@ def _rebind(model, opt, new_params, new_moments):
 
 
 def _prepare(opt):
+    from .native_trainer import NativeTrainer
     from .trainer import FrameTrainer
-    if isinstance(opt, FrameTrainer):
+    if isinstance(opt, (FrameTrainer, NativeTrainer)):
         opt.begin_density_control()
 
 

@@ -9,7 +9,8 @@ of the optimizer state, and the error-timestamp bookkeeping that picks the extra
     expand_duration(model, opt, duration)
     adjust_temp_opa(model, opt)
 
-`opt` is as in ex4dgs_amd.densify: torch.optim.RAdam / FusedRAdam over the reference's 15 groups, a trainer.FrameTrainer, or None.
+`opt` is as in ex4dgs_amd.densify: torch.optim.RAdam / FusedRAdam over the reference's 15 groups, a trainer.FrameTrainer, a
+native_trainer.NativeTrainer, or None.
 No CPU fallback: everything runs on a ROCm device.  DESIGN.md section 7 lists the quirks kept.
 """
 import ctypes as C
@@ -249,8 +250,8 @@ def expand_duration(model, opt, duration):
         _abi.call("ex4d_growth_expand_opacity", ptr(center), ptr(var), ptr(new["_opacity_duration_center"]), ptr(new["_opacity_duration_var"]), nd,
                   _f32(shift_i), _f32((duration + model.time_shift) / model.interval - 0.5),
                   _f32((model.time_shift + model.duration - 1) / model.interval), stream)
+    model.duration = duration            # before the optimizer rebinds: a NativeTrainer reads the model's time constants when it does
     _replace(model, opt, new)
-    model.duration = duration
     if hasattr(model, "_drop_fused_cache"):
         model._drop_fused_cache()
     return True

@@ -44,6 +44,12 @@ enum {
 int ex4d_densify_stats(float *stats_s, int64_t ns, float *stats_d, int64_t nd, const int32_t *radii, const float *vgrad,
                        const float *egrad, float timestamp, int32_t flags, void *stream);
 
+/* ---- the gate of prune_nan_points (:1230, :1234: isnan().any() per group) without a read-back: flags2[0] = any(isnan(a[0 .. n_a))),
+ * flags2[1] likewise for b; either array may be empty (n = 0, pointer then unused, may be NULL).  a and b need only float alignment.
+ * flags2 (device int32[2]) is fully written: cleared by a kernel of the library, then one launch streams both arrays.  No atomics, no
+ * host synchronisation (graph-capturable). */
+int ex4d_nan_any(const float *a, int64_t n_a, const float *b, int64_t n_b, int32_t *flags2, void *stream);
+
 /* ---- classification + compaction of one group */
 enum { EX4D_PLAN_DENSIFY = 0, EX4D_PLAN_PRUNE_INVISIBLE = 1, EX4D_PLAN_PRUNE_SMALL = 2, EX4D_PLAN_PRUNE_NAN = 3 };
 

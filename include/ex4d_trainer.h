@@ -13,12 +13,16 @@
  * a frame needs more), so the only host <-> device synchronisation of an iteration is the instance-count read-back the reference has
  * too (rasterizer_impl.cu:298-299), which overlaps the depth sort.
  *
- * SCOPE: this is the render + L1/SSIM + regularisers + RAdam core of the iteration, not the reference's whole loop.  The regularisers
- * static_reg / motion_reg / rot_reg (train.py:156-168) are off until ex4d_trainer_set_regularizers gives them weights; the keyframe
- * terms, dense over all K, are formed inside ex4d_radam_step_sliced_reg, so the keyframe gradients stay slices.  Not included (they
- * live in the reference's Python policy layer, out of SURVEY.md 8's scope): the
- * l1_accum error-map hook on the flow output (train.py:149-152: dL_dout_flow is NULL here, so viewspace_l1points stays zero),
- * densification / pruning and their statistics.  What the loop changes over time is settable: ex4d_trainer_set_lr (the position
+ * SCOPE: this is the render + L1/SSIM + regularisers + RAdam core of the iteration, and -- through ex4d_trainer_step_ex -- the
+ * per-frame steps the reference's default schedule adds around it: the l1_accum error hook on the flow output (train.py:148-153:
+ * viewspace_l1points.grad is output 7), the densification statistics (train.py:199-216, ex4d_densify_stats on the trainer's own
+ * tensors), an iteration whose optimizer step is skipped (train.py densifies before optimizer.step()) and the NaN gate of
+ * prune_nan_points (train.py:253).  The regularisers static_reg / motion_reg / rot_reg (train.py:156-168) are off until
+ * ex4d_trainer_set_regularizers gives them weights; the keyframe terms, dense over all K, are formed inside
+ * ex4d_radam_step_sliced_reg, so the keyframe gradients stay slices.  Density control and growth themselves (ex4d_densify.h) change
+ * the row counts: the caller reads the moments (ex4d_trainer_read 200 + i / 300 + i) and the step count, destroys the trainer,
+ * creates one over the new tensors and writes them back (ex4d_trainer_write, ex4d_trainer_set_step); an in-place resize of the
+ * workspace is not part of this interface.  What the loop changes over time is settable: ex4d_trainer_set_lr (the position
  * learning-rate schedule, update_learning_rate) and ex4d_trainer_set_sh_degree (oneupSHdegree every 1000 iterations).
  * _opacity_duration_var's gradient is read through nan_to_num like train.py:244-247 does before optimizer.step().
  *
@@ -72,6 +76,31 @@ void ex4d_trainer_time_scalars(const Ex4dTrainerConfig *cfg, double timestamp, s
 int ex4d_trainer_step(Ex4dTrainer *t, double timestamp, const float *viewmatrix, const float *projmatrix, const float *campos,
                       const float *background, const float *gt_image, void *stream, int32_t *num_rendered);
 
+/* The same iteration with the per-frame policy steps of the reference's loop; opt = NULL is ex4d_trainer_step. */
+typedef struct Ex4dTrainerStepOptions {
+    int32_t l1_accum;        /* 1: train.py:148-153 -- stack([acc[0], l1_errors, ssim_errors]) (output 8) is dL_dout_flow; dir3D stays
+                                NULL (zeros), so dL_ddir [P,3] is the per-Gaussian error gradient (e0, e1, e2): output 7 */
+    int32_t skip_optimizer;  /* 1: gradients and statistics only; no regulariser backward, no RAdam, step count not advanced */
+    int32_t stats_flags;     /* EX4D_DENSIFY_* of ex4d_densify.h, 0 = no statistics; PRUNE_STATS / L1_STATS need l1_accum.  Counted once
+                                per step, after an overflowing asynchronous frame has been re-run */
+    int32_t nan_census;      /* 1: after the optimizer step, flag NaN rows of _xyz / _xyz_motion (ex4d_nan_any) for ex4d_trainer_report */
+    float *stats_s, *stats_d;   /* caller-owned [9,Ns] / [9,Nd] blocks (DensityStats.static / .dynamic) */
+} Ex4dTrainerStepOptions;
+int ex4d_trainer_step_ex(Ex4dTrainer *t, double timestamp, const float *viewmatrix, const float *projmatrix, const float *campos,
+                         const float *background, const float *gt_image, void *stream, int32_t *num_rendered,
+                         const Ex4dTrainerStepOptions *opt);
+
+/* What a loop reads back per iteration: at the end of every ex4d_trainer_step_ex with options the loss word and the two census flags
+ * are copied to pinned host memory behind an event; ex4d_trainer_report waits for that event -- the one wait that stands for
+ * loss.item() and the count read-back of prune_nan_points.  nan_static / nan_dynamic: 1 = some element of _xyz / _xyz_motion is NaN
+ * (0 when the step did not ask for the census).  EX4D_ERR_ARG before the first such step. */
+typedef struct Ex4dTrainerReport {
+    float loss;
+    int32_t nan_static, nan_dynamic;
+    int32_t reserved;
+} Ex4dTrainerReport;
+int ex4d_trainer_report(Ex4dTrainer *t, Ex4dTrainerReport *out);
+
 /* The per-group learning rates (15, PARAM order) / the active SH degree used from the next step on: update_learning_rate
  * (c_gaussian_model.py:451-470) and oneupSHdegree (train.py:113-114) of the reference change them during training. */
 int ex4d_trainer_set_lr(Ex4dTrainer *t, const double *lr15);
@@ -91,15 +120,24 @@ int ex4d_trainer_set_regularizers(Ex4dTrainer *t, double static_reg, double moti
 /* Device pointers into the trainer's workspace, valid until the next step / destroy:
  * what = 0 loss [1], 1 render [3,H,W], 2 radii int32 [P], 3 dL_dmeans2D [P,3] (viewspace gradient, densification statistics),
  *        4 depth [1,H,W], 5 acc [1,H,W], 6 regularisers float[4] = {static mean, motion mean, rot mean, weighted sum} of the last step
- *        that had them on (zeros before); the loss of what = 0 stays the L1/SSIM loss. */
+ *        that had them on (zeros before); the loss of what = 0 stays the L1/SSIM loss,
+ *        7 error gradient [P,3] (dL_ddir: (e0, e1, e2) of the last l1_accum step), 8 hook [3,H,W] (plane 0 is
+ *        output 5; planes 1, 2 = l1_errors, ssim_errors of the last l1_accum step). */
 const void *ex4d_trainer_output(const Ex4dTrainer *t, int32_t what);
 /* Gradient of parameter i of the last step: dense [shape of the parameter] except i = 7 (_xyz_motion: [Nd,4,3]) and i = 8
  * (_rotation_motion: [Nd,2,4]), the slices of ex4d_attributes_backward_sliced; slices4 (host int32[4], may be NULL) receives
  * {xyz first, 4, rotation first, 2}. */
 const float *ex4d_trainer_grad(const Ex4dTrainer *t, int32_t i, int32_t *slices4);
 /* Asynchronous device-to-device copy of one of the buffers above into caller memory (bindings that cannot wrap a raw pointer):
- * what = 0..6 as in ex4d_trainer_output, 100 + i = gradient of parameter i.  `bytes` must not exceed the buffer's size. */
+ * what = 0..8 as in ex4d_trainer_output, 100 + i = gradient of parameter i, 200 + i = exp_avg and 300 + i = exp_avg_sq of parameter i
+ * (optimizer = 1 only; the parameter's shape).  `bytes` must not exceed the buffer's size. */
 int ex4d_trainer_read(const Ex4dTrainer *t, int32_t what, void *dst, size_t bytes, void *stream);
+/* The inverse of ex4d_trainer_read for the optimizer state: what = 200 + i / 300 + i only; src is device memory.  With the step count
+ * below this moves a trainer's state into the one created after density control replaced the parameter tensors. */
+int ex4d_trainer_write(Ex4dTrainer *t, int32_t what, const void *src, size_t bytes, void *stream);
+/* RAdam's step count (the number of optimizer steps applied so far). */
+int ex4d_trainer_get_step(const Ex4dTrainer *t, int64_t *step);
+int ex4d_trainer_set_step(Ex4dTrainer *t, int64_t step);
 /* bytes of device memory the trainer holds (workspace + optimizer state + arenas) */
 size_t ex4d_trainer_bytes(const Ex4dTrainer *t);
 
