@@ -171,7 +171,9 @@ PROTOTYPES = {
         _value("ex4d_loss_last_error", text),
         _value("ex4d_l1_ssim_scratch_floats", size, i32, i32),
         _status("ex4d_l1_ssim_forward", i32, i32, i32, vp, vp, f32, *[vp] * 7),
-        _status("ex4d_l1_ssim_backward", i32, i32, i32, vp, vp, f32, *[vp] * 5))),
+        _status("ex4d_l1_ssim_backward", i32, i32, i32, vp, vp, f32, *[vp] * 5),
+        _status("ex4d_l1_ssim_forward_u8", i32, i32, vp, vp, i32, vp, f32, *[vp] * 7),
+        _status("ex4d_l1_ssim_backward_u8", i32, i32, vp, vp, i32, vp, f32, *[vp] * 5))),
     "ex4d_optim.h": ("ex4d_optim_last_error", (
         _value("ex4d_optim_last_error", text),
         _status("ex4d_radam_step", P(Ex4dRadamTensor), i32, f64, f64, f64, vp),
@@ -209,6 +211,7 @@ PROTOTYPES = {
         _value("ex4d_trainer_time_scalars", None, P(Ex4dTrainerConfig), f64, P(Ex4dAttrParams)),
         _status("ex4d_trainer_step", vp, f64, *[vp] * 6, P(i32)),
         _status("ex4d_trainer_step_ex", vp, f64, *[vp] * 6, P(i32), P(Ex4dTrainerStepOptions)),
+        _status("ex4d_trainer_step_u8", vp, f64, *[vp] * 5, i32, vp, vp, P(i32), P(Ex4dTrainerStepOptions)),
         _status("ex4d_trainer_report", vp, P(Ex4dTrainerReport)),
         _status("ex4d_trainer_set_lr", vp, P(f64)),
         _status("ex4d_trainer_set_sh_degree", vp, i32),

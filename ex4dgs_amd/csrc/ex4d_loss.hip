@@ -16,6 +16,17 @@
 // Forward emits the loss partial sums, the two error maps and, per pixel and channel, the three partial derivatives of the SSIM map
 // the backward needs; backward convolves those three maps with the same (symmetric) window and combines them with the pixel values:
 //     d(sum ssim)/dx_p = conv(A)_p + 2 x_p conv(B)_p + y_p conv(C)_p,   A = dS/dmu1, B = dS/dE[x^2], C = dS/dE[xy].
+//
+// GROUND TRUTH AS DECODED (ex4d_l1_ssim_*_u8): both kernels are templates over the ground truth's element type -- float32 [C,H,W] planes,
+// or uint8 [H,W,S] pixels (S = 3 or 4, as an image decoder leaves them) looked up in a 256-entry float table, which the uint8
+// instantiations take as one more kernel argument.  Everything behind the load is the same code, so the two agree bit for bit on equal
+// values; the float instantiations keep the signature and the loads they had.  THE TABLE travels in the kernel
+// arguments (1 KB by value, as the 11 window taps do) and every workgroup copies it into LDS with one load per thread: the call
+// allocates nothing, copies nothing host-to-device, does not synchronise, and a captured graph holds the table by value.  A table in
+// global memory would need a per-call upload or an owner; constant-indexed kernel arguments cannot be indexed per lane.  LDS: 76 064 +
+// 1 024 B forward, 58 752 + 1 024 B backward, both within the 80 KB of two workgroups per CU.  The bytes are fetched with byte loads
+// (any alignment: frame i of a resident [N,H,W,3] store starts at an odd address for odd H W); the forward keeps the BYTE in flight
+// across the convolution and looks it up when the row is committed to LDS, so the global load stays hidden as the float one is.
 #include "ex4d_internal.h"
 #include "../../include/ex4d_loss.h"
 #include <cstdio>
@@ -35,12 +46,29 @@ namespace {
 static_assert(sizeof(float) * (2 * 2 * CG * RPI * (SIN + 2) + CG * 5 * RING * SW + 8) <= 80 * 1024, "l1_ssim_fwd_kernel: two workgroups per CU need <= 80 KB of LDS each");
 static_assert(sizeof(float) * (2 * 3 * CG * RPI * (SIN + 2) + CG * 3 * RING * SW) <= 80 * 1024, "l1_ssim_bwd_kernel: two workgroups per CU need <= 80 KB of LDS each");
 
+static_assert(sizeof(float) * (2 * 2 * CG * RPI * (SIN + 2) + CG * 5 * RING * SW + 8 + 256) <= 80 * 1024, "l1_ssim_fwd_kernel<uint8_t>: the table joins the same budget");
+static_assert(sizeof(float) * (2 * 3 * CG * RPI * (SIN + 2) + CG * 3 * RING * SW + 256) <= 80 * 1024, "l1_ssim_bwd_kernel<uint8_t>: the table joins the same budget");
+
 struct Window { float w[EX4D_SSIM_WINDOW]; };
 
-__device__ __forceinline__ float load_or_zero(const float *__restrict__ p, int x, int y, int W, int H)
+// uint8 ground truth: what the _u8 instantiations take as their LAST kernel argument (the float ones have no such argument and keep the
+// signature, and so the code, they had): bytes per pixel and the value of each byte
+struct PixelTable { int S; float v[256]; };
+struct PixelLds { const float *v; int S; };             // the workgroup's copy
+
+// 256 threads, one entry each; the caller's next barrier publishes it.  (A function of its own so that only the _u8 instantiations own
+// the 1 KB.)
+__device__ __forceinline__ PixelLds table_to_lds(const PixelTable &t)
 {
-    return (x >= 0 && x < W && y >= 0 && y < H) ? p[(size_t)y * W + x] : 0.f;    // zero padding (conv2d padding=5)
+    __shared__ float s_table[256];
+    s_table[threadIdx.x] = t.v[threadIdx.x];
+    return PixelLds{ s_table, t.S };
 }
+__device__ __forceinline__ PixelLds table_to_lds() { return PixelLds{ nullptr, 0 }; }
+
+// a byte in flight in a float register: its value as the register's bits, -1 for zero padding (conv2d padding=5 is the float 0, never v[0])
+__device__ __forceinline__ float byte_bits(bool ok, const uint8_t *__restrict__ p, size_t o) { return __int_as_float(ok ? (int)p[o] : -1); }
+__device__ __forceinline__ float byte_value(float bits, const float *v) { const int u = __float_as_int(bits); return u >= 0 ? v[u] : 0.f; }
 
 // workgroup -> (strip, segment): consecutive workgroup ids round-robin over the 8 XCDs, so XCD x takes the contiguous run of work items
 // [x * per, (x + 1) * per) in row-major (segment, strip) order: horizontally neighbouring strips share their halo columns in one L2
@@ -50,13 +78,16 @@ __device__ __forceinline__ int work_item_of_block(int nwork)
     return (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
 }
 
+template <typename T, typename... Table>
 __global__ __launch_bounds__(256) void l1_ssim_fwd_kernel(int C, int H, int W, const float *__restrict__ img,
-    const float *__restrict__ gt, Window win, float *__restrict__ l1_errors, float *__restrict__ ssim_errors,
-    float *__restrict__ dmaps, float *__restrict__ partials, int nsx, int nsy)
+    const T *__restrict__ gt, Window win, float *__restrict__ l1_errors, float *__restrict__ ssim_errors,
+    float *__restrict__ dmaps, float *__restrict__ partials, int nsx, int nsy, Table... table)
 {
+    constexpr bool kBytes = sizeof...(Table) != 0;
     __shared__ float s_in[2][2][CG][RPI][SIN + 2];      // [buffer][x | y][channel][row][column]
     __shared__ float s_ring[CG][5][RING][SW];           // row-pass results of the last RING image rows
     __shared__ float s_red[2][4];
+    const PixelLds px8 = table_to_lds(table...);        // (published by the barrier in front of the first fetch)
     const int nwork = nsx * nsy;
     const int wi = work_item_of_block(nwork);
     const int col = threadIdx.x & (SW - 1), rsub = threadIdx.x >> 6;
@@ -86,16 +117,31 @@ __global__ __launch_bounds__(256) void l1_ssim_fwd_kernel(int C, int H, int W, c
 #pragma unroll
                 for (int pl = 0; pl < 2 * CG; pl++) {
                     const int ch = pl % CG;
-                    const float *src = ((pl / CG) ? gt : img) + (size_t)(c0 + ch) * HW;
-                    rm[pl] = (okm && ch < nc) ? src[om] : 0.f;       // zero padding (conv2d padding=5)
-                    rh[pl] = (okh && ch < nc) ? src[oh] : 0.f;
+                    if constexpr (kBytes) {
+                        if (pl / CG) {                   // the BYTE stays in flight; commit looks it up
+                            rm[pl] = byte_bits(okm && ch < nc, gt, om * px8.S + (c0 + ch));
+                            rh[pl] = byte_bits(okh && ch < nc, gt, oh * px8.S + (c0 + ch));
+                        } else {
+                            const float *src = img + (size_t)(c0 + ch) * HW;
+                            rm[pl] = (okm && ch < nc) ? src[om] : 0.f;
+                            rh[pl] = (okh && ch < nc) ? src[oh] : 0.f;
+                        }
+                    } else {
+                        const float *src = ((pl / CG) ? gt : img) + (size_t)(c0 + ch) * HW;
+                        rm[pl] = (okm && ch < nc) ? src[om] : 0.f;       // zero padding (conv2d padding=5)
+                        rh[pl] = (okh && ch < nc) ? src[oh] : 0.f;
+                    }
                 }
             };
             auto commit = [&](int buf) {
 #pragma unroll
                 for (int pl = 0; pl < 2 * CG; pl++) {
-                    s_in[buf][pl / CG][pl % CG][rsub][col] = rm[pl];
-                    if (has_halo) s_in[buf][pl / CG][pl % CG][hrow][hcol] = rh[pl];
+                    float vm = rm[pl], vh = rh[pl];
+                    if constexpr (kBytes) {
+                        if (pl / CG) { vm = byte_value(vm, px8.v); vh = byte_value(vh, px8.v); }
+                    }
+                    s_in[buf][pl / CG][pl % CG][rsub][col] = vm;
+                    if (has_halo) s_in[buf][pl / CG][pl % CG][hrow][hcol] = vh;
                 }
             };
             __syncthreads();                             // (the previous channel group is done with both buffers and the ring)
@@ -206,15 +252,18 @@ __global__ __launch_bounds__(256) void l1_ssim_finish_kernel(int nblocks, const 
     }
 }
 
+template <typename T, typename... Table>
 __global__ __launch_bounds__(256) void l1_ssim_bwd_kernel(int C, int H, int W, const float *__restrict__ img,
-    const float *__restrict__ gt, Window win, const float *__restrict__ dmaps, const float *__restrict__ grad_loss,
-    float lambda_dssim, float inv_count, float *__restrict__ grad_img, int nsx, int nsy)
+    const T *__restrict__ gt, Window win, const float *__restrict__ dmaps, const float *__restrict__ grad_loss,
+    float lambda_dssim, float inv_count, float *__restrict__ grad_img, int nsx, int nsy, Table... table)
 {
+    constexpr bool kBytes = sizeof...(Table) != 0;
     __shared__ float s_in[2][3][CG][RPI][SIN + 2];      // [buffer][map A | B | C][channel][row][column]
     __shared__ float s_ring[CG][3][RING][SW];
     const int nwork = nsx * nsy;
     const int wi = work_item_of_block(nwork);
     if (wi >= nwork) return;                             // (uniform: the whole workgroup)
+    const PixelLds px8 = table_to_lds(table...);        // (read in the column pass, barriers later)
     const int col = threadIdx.x & (SW - 1), rsub = threadIdx.x >> 6;
     const size_t HW = (size_t)H * W;
     const float gl = grad_loss[0];
@@ -280,7 +329,10 @@ __global__ __launch_bounds__(256) void l1_ssim_bwd_kernel(int C, int H, int W, c
                         ca += wk * s_ring[ch][0][slot][col]; cb += wk * s_ring[ch][1][slot][col]; ccv += wk * s_ring[ch][2][slot][col];
                     }
                     const size_t o = (size_t)(c0 + ch) * HW + (size_t)(y0 + ro) * W + px;
-                    const float xv = img[o], yv = gt[o];
+                    float yv;
+                    if constexpr (kBytes) yv = px8.v[gt[((size_t)(y0 + ro) * W + px) * px8.S + (c0 + ch)]];
+                    else yv = gt[o];
+                    const float xv = img[o];
                     const float dssim = ca + 2.f * xv * cb + yv * ccv;                   // d(sum of ssim_map)/dx_p
                     const float diff = xv - yv;
                     const float sgn = (diff > 0.f) ? 1.f : ((diff < 0.f) ? -1.f : 0.f);  // d|x - y|/dx
@@ -301,15 +353,57 @@ bool check_args(int C, int H, int W, const void *a, const void *b, const float *
     return true;
 }
 
+static inline int strips_of(int W) { return (W + SW - 1) / SW; }
+static inline int segments_of(int H) { return (H + SEG - 1) / SEG; }
+static inline int blocks_of(int H, int W) { return 8 * ((strips_of(W) * segments_of(H) + 7) / 8); }       // (padded: the XCD-aware work-item map)
+
+// the two launches of a forward / the one of a backward, for either kind of ground truth (the arguments were checked by the caller)
+template <typename T, typename... Table>
+int launch_forward(int C, int H, int W, const float *img, const T *gt, float lambda_dssim, const float *window, float *loss,
+                          float *l1_errors, float *ssim_errors, float *dmaps, float *scratch, hipStream_t stream, const Table &... table)
+{
+    Window win;
+    for (int i = 0; i < EX4D_SSIM_WINDOW; i++) win.w[i] = window[i];
+    const int nblocks = blocks_of(H, W);
+    hipLaunchKernelGGL((l1_ssim_fwd_kernel<T, Table...>), dim3(nblocks), dim3(256), 0, stream, C, H, W, img, gt, win, l1_errors, ssim_errors, dmaps, scratch,
+                       strips_of(W), segments_of(H), table...);
+    hipLaunchKernelGGL(l1_ssim_finish_kernel, dim3(1), dim3(256), 0, stream, nblocks, scratch,
+                       1.0 / ((double)C * H * W), lambda_dssim, loss);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { snprintf(g_loss_err, sizeof(g_loss_err), "launch failed: %s", hipGetErrorString(e)); return EX4D_ERR_HIP; }
+    return EX4D_OK;
+}
+
+template <typename T, typename... Table>
+int launch_backward(int C, int H, int W, const float *img, const T *gt, float lambda_dssim, const float *window, const float *dmaps,
+                           const float *grad_loss, float *grad_img, hipStream_t stream, const Table &... table)
+{
+    Window win;
+    for (int i = 0; i < EX4D_SSIM_WINDOW; i++) win.w[i] = window[i];
+    hipLaunchKernelGGL((l1_ssim_bwd_kernel<T, Table...>), dim3(blocks_of(H, W)), dim3(256), 0, stream, C, H, W, img, gt, win, dmaps, grad_loss, lambda_dssim,
+                       (float)(1.0 / ((double)C * H * W)), grad_img, strips_of(W), segments_of(H), table...);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { snprintf(g_loss_err, sizeof(g_loss_err), "launch failed: %s", hipGetErrorString(e)); return EX4D_ERR_HIP; }
+    return EX4D_OK;
+}
+
+// uint8 pixels + the host table (NULL: u / 255, the division PILtoTorch does, utils/general_utils.py:25) as the kernels take them
+bool pixels_of(const uint8_t *gt, int32_t pixel_stride, const float *lut, PixelTable *out)
+{
+    if (!gt || (pixel_stride != 3 && pixel_stride != 4)) {
+        snprintf(g_loss_err, sizeof(g_loss_err), !gt ? "bad argument" : "pixel_stride %d: uint8 ground truth has 3 or 4 bytes per pixel", (int)pixel_stride);
+        return false;
+    }
+    out->S = pixel_stride;
+    for (int u = 0; u < 256; u++) out->v[u] = lut ? lut[u] : (float)u / 255.0f;
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
 
 const char *ex4d_loss_last_error(void) { return g_loss_err; }
-
-static inline int strips_of(int W) { return (W + SW - 1) / SW; }
-static inline int segments_of(int H) { return (H + SEG - 1) / SEG; }
-static inline int blocks_of(int H, int W) { return 8 * ((strips_of(W) * segments_of(H) + 7) / 8); }       // (padded: the XCD-aware work-item map)
 
 size_t ex4d_l1_ssim_scratch_floats(int32_t H, int32_t W) { return 2 * (size_t)blocks_of(H, W) + 64; }
 
@@ -319,17 +413,7 @@ int ex4d_l1_ssim_forward(int32_t C, int32_t H, int32_t W, const float *img, cons
 {
     g_loss_err[0] = 0;
     if (!check_args(C, H, W, img, gt, window) || !loss || !dmaps || !scratch) { snprintf(g_loss_err, sizeof(g_loss_err), "bad argument"); return EX4D_ERR_ARG; }
-    hipStream_t stream = (hipStream_t)stream_;
-    Window win;
-    for (int i = 0; i < EX4D_SSIM_WINDOW; i++) win.w[i] = window[i];
-    const int nblocks = blocks_of(H, W);
-    hipLaunchKernelGGL(l1_ssim_fwd_kernel, dim3(nblocks), dim3(256), 0, stream, C, H, W, img, gt, win, l1_errors, ssim_errors, dmaps, scratch,
-                       strips_of(W), segments_of(H));
-    hipLaunchKernelGGL(l1_ssim_finish_kernel, dim3(1), dim3(256), 0, stream, nblocks, scratch,
-                       1.0 / ((double)C * H * W), lambda_dssim, loss);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { snprintf(g_loss_err, sizeof(g_loss_err), "launch failed: %s", hipGetErrorString(e)); return EX4D_ERR_HIP; }
-    return EX4D_OK;
+    return launch_forward(C, H, W, img, gt, lambda_dssim, window, loss, l1_errors, ssim_errors, dmaps, scratch, (hipStream_t)stream_);
 }
 
 int ex4d_l1_ssim_backward(int32_t C, int32_t H, int32_t W, const float *img, const float *gt, float lambda_dssim,
@@ -337,14 +421,28 @@ int ex4d_l1_ssim_backward(int32_t C, int32_t H, int32_t W, const float *img, con
 {
     g_loss_err[0] = 0;
     if (!check_args(C, H, W, img, gt, window) || !dmaps || !grad_loss || !grad_img) { snprintf(g_loss_err, sizeof(g_loss_err), "bad argument"); return EX4D_ERR_ARG; }
-    hipStream_t stream = (hipStream_t)stream_;
-    Window win;
-    for (int i = 0; i < EX4D_SSIM_WINDOW; i++) win.w[i] = window[i];
-    hipLaunchKernelGGL(l1_ssim_bwd_kernel, dim3(blocks_of(H, W)), dim3(256), 0, stream, C, H, W, img, gt, win, dmaps, grad_loss, lambda_dssim,
-                       (float)(1.0 / ((double)C * H * W)), grad_img, strips_of(W), segments_of(H));
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { snprintf(g_loss_err, sizeof(g_loss_err), "launch failed: %s", hipGetErrorString(e)); return EX4D_ERR_HIP; }
-    return EX4D_OK;
+    return launch_backward(C, H, W, img, gt, lambda_dssim, window, dmaps, grad_loss, grad_img, (hipStream_t)stream_);
+}
+
+int ex4d_l1_ssim_forward_u8(int32_t H, int32_t W, const float *img, const uint8_t *gt, int32_t pixel_stride, const float *lut,
+                            float lambda_dssim, const float *window, float *loss, float *l1_errors, float *ssim_errors, float *dmaps,
+                            float *scratch, void *stream_)
+{
+    g_loss_err[0] = 0;
+    PixelTable px;
+    if (!check_args(3, H, W, img, gt, window) || !loss || !dmaps || !scratch) { snprintf(g_loss_err, sizeof(g_loss_err), "bad argument"); return EX4D_ERR_ARG; }
+    if (!pixels_of(gt, pixel_stride, lut, &px)) return EX4D_ERR_ARG;
+    return launch_forward(3, H, W, img, gt, lambda_dssim, window, loss, l1_errors, ssim_errors, dmaps, scratch, (hipStream_t)stream_, px);
+}
+
+int ex4d_l1_ssim_backward_u8(int32_t H, int32_t W, const float *img, const uint8_t *gt, int32_t pixel_stride, const float *lut,
+                             float lambda_dssim, const float *window, const float *dmaps, const float *grad_loss, float *grad_img, void *stream_)
+{
+    g_loss_err[0] = 0;
+    PixelTable px;
+    if (!check_args(3, H, W, img, gt, window) || !dmaps || !grad_loss || !grad_img) { snprintf(g_loss_err, sizeof(g_loss_err), "bad argument"); return EX4D_ERR_ARG; }
+    if (!pixels_of(gt, pixel_stride, lut, &px)) return EX4D_ERR_ARG;
+    return launch_backward(3, H, W, img, gt, lambda_dssim, window, dmaps, grad_loss, grad_img, (hipStream_t)stream_, px);
 }
 
 }  // extern "C"

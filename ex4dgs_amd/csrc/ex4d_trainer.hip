@@ -222,12 +222,23 @@ int ex4d_trainer_step(Ex4dTrainer *t, double timestamp, const float *viewmatrix,
     return ex4d_trainer_step_ex(t, timestamp, viewmatrix, projmatrix, campos, background, gt_image, stream, num_rendered, nullptr);
 }
 
-int ex4d_trainer_step_ex(Ex4dTrainer *t, double timestamp, const float *viewmatrix, const float *projmatrix, const float *campos,
-                         const float *background, const float *gt_image, void *stream, int32_t *num_rendered,
-                         const Ex4dTrainerStepOptions *opt)
+// the frame's ground truth: float32 [3,H,W] planes (f32) or uint8 [H,W,S] pixels with their host table (u8; include/ex4d_loss.h)
+struct GroundTruth {
+    const float *f32;
+    const uint8_t *u8;
+    int32_t pixel_stride;
+    const float *lut;
+};
+
+// The one body of ex4d_trainer_step, _step_ex and _step_u8: they differ in which pair of loss entry points reads the ground truth.
+static int step_body(Ex4dTrainer *t, double timestamp, const float *viewmatrix, const float *projmatrix, const float *campos,
+                     const float *background, const GroundTruth &gt, void *stream, int32_t *num_rendered,
+                     const Ex4dTrainerStepOptions *opt)
 {
     t_err[0] = 0;
-    if (!t || !viewmatrix || !projmatrix || !campos || !background || !gt_image) return tfail(EX4D_ERR_ARG, "null argument");
+    if (!t || !viewmatrix || !projmatrix || !campos || !background || (!gt.f32 && !gt.u8)) return tfail(EX4D_ERR_ARG, "null argument");
+    if (gt.u8 && gt.pixel_stride != 3 && gt.pixel_stride != 4)
+        return tfail(EX4D_ERR_ARG, "pixel_stride %d: uint8 ground truth has 3 or 4 bytes per pixel", (int)gt.pixel_stride);
     const Ex4dTrainerConfig &c = t->cfg;
     const bool l1_accum = opt && opt->l1_accum, skip_optimizer = opt && opt->skip_optimizer, census = opt && opt->nan_census;
     const int32_t stats_flags = opt ? opt->stats_flags : 0;
@@ -280,9 +291,13 @@ int ex4d_trainer_step_ex(Ex4dTrainer *t, double timestamp, const float *viewmatr
             R = (int32_t)t->capacity;                        // the backward lays the buffers out for the capacity
         }
 
-        if (ex4d_l1_ssim_forward(3, c.H, c.W, t->color, gt_image, c.lambda_dssim, c.window, t->loss, l1_errors, ssim_errors, t->dmaps, t->loss_scratch, stream))
+        // (a frame re-run after an overflow reads the same ground truth again)
+        if (gt.u8 ? ex4d_l1_ssim_forward_u8(c.H, c.W, t->color, gt.u8, gt.pixel_stride, gt.lut, c.lambda_dssim, c.window, t->loss, l1_errors, ssim_errors,
+                                            t->dmaps, t->loss_scratch, stream)
+                  : ex4d_l1_ssim_forward(3, c.H, c.W, t->color, gt.f32, c.lambda_dssim, c.window, t->loss, l1_errors, ssim_errors, t->dmaps, t->loss_scratch, stream))
             return tfail(EX4D_ERR_HIP, "loss forward: %s", ex4d_loss_last_error());
-        if (ex4d_l1_ssim_backward(3, c.H, c.W, t->color, gt_image, c.lambda_dssim, c.window, t->dmaps, t->grad_loss, t->grad_img, stream))
+        if (gt.u8 ? ex4d_l1_ssim_backward_u8(c.H, c.W, t->color, gt.u8, gt.pixel_stride, gt.lut, c.lambda_dssim, c.window, t->dmaps, t->grad_loss, t->grad_img, stream)
+                  : ex4d_l1_ssim_backward(3, c.H, c.W, t->color, gt.f32, c.lambda_dssim, c.window, t->dmaps, t->grad_loss, t->grad_img, stream))
             return tfail(EX4D_ERR_HIP, "loss backward: %s", ex4d_loss_last_error());
 
         rc = ex4d_backward_split_sh(&prm, R, background, t->means3D, t->radii, &sh, t->scales, t->rotations, nullptr, viewmatrix, projmatrix, campos,
@@ -370,6 +385,20 @@ int ex4d_trainer_step_ex(Ex4dTrainer *t, double timestamp, const float *viewmatr
         t->report_census = census;
     }
     return EX4D_OK;
+}
+
+int ex4d_trainer_step_ex(Ex4dTrainer *t, double timestamp, const float *viewmatrix, const float *projmatrix, const float *campos,
+                         const float *background, const float *gt_image, void *stream, int32_t *num_rendered,
+                         const Ex4dTrainerStepOptions *opt)
+{
+    return step_body(t, timestamp, viewmatrix, projmatrix, campos, background, GroundTruth{ gt_image, nullptr, 0, nullptr }, stream, num_rendered, opt);
+}
+
+int ex4d_trainer_step_u8(Ex4dTrainer *t, double timestamp, const float *viewmatrix, const float *projmatrix, const float *campos,
+                         const float *background, const uint8_t *gt_u8, int32_t pixel_stride, const float *lut, void *stream,
+                         int32_t *num_rendered, const Ex4dTrainerStepOptions *opt)
+{
+    return step_body(t, timestamp, viewmatrix, projmatrix, campos, background, GroundTruth{ nullptr, gt_u8, pixel_stride, lut }, stream, num_rendered, opt);
 }
 
 int ex4d_trainer_report(Ex4dTrainer *t, Ex4dTrainerReport *out)

@@ -5,6 +5,9 @@ include/ex4d_loss.h, instead of the reference's l1_loss + ssim and their autogra
     loss, l1_errors, ssim_errors = l1_ssim_loss(image, gt_image, lambda_dssim)
     loss, l1_errors, ssim_errors, hook_tensor = l1_ssim_loss(image, gt_image, lambda_dssim, acc=acc)
 
+`gt_image` may also be the frame as decoded: a uint8 [H,W,3|4] device tensor (ex4dgs_amd.frames) whose bytes the kernels turn into
+floats on load through `lut=` (a CPU float32 [256] table, default frames.gt_lut()); the float image is never formed.
+
 `loss` is differentiable w.r.t. `image`; the two [H,W] error maps are the per-pixel channel means the reference hands
 to its densification statistics (train.py:149-150) and carry no gradient.  No CPU fallback.
 """
@@ -64,17 +67,65 @@ class _L1SSIM(torch.autograd.Function):
         return grad, None, None, None
 
 
-def l1_ssim_loss(image, gt_image, lambda_dssim=0.2, acc=None):
+class _L1SSIMBytes(torch.autograd.Function):
+    """The same op on uint8 [H,W,S] ground truth: ex4d_l1_ssim_forward_u8 / _backward_u8 (lut None = NULL: u / 255)."""
+    @staticmethod
+    def forward(ctx, image, gt, lambda_dssim, errors, lut):
+        lib = _lib()
+        if not image.is_cuda:
+            raise RuntimeError(f"image is on {image.device}: the fused L1+SSIM loss only runs on a ROCm GPU (no CPU fallback)")
+        if image.dim() != 3 or image.shape[0] != 3 or image.dtype != torch.float32 or gt.dim() != 3 or gt.shape[2] not in (3, 4) \
+                or tuple(gt.shape[:2]) != tuple(image.shape[1:]) or gt.device != image.device:
+            raise RuntimeError("uint8 gt_image must be [H,W,3] or [H,W,4] on the ROCm device of a float32 [3,H,W] image")
+        if lut is not None and (lut.device.type != "cpu" or lut.dtype != torch.float32 or tuple(lut.shape) != (256,)):
+            raise RuntimeError("lut must be a CPU float32 [256] tensor (frames.gt_lut)")
+        image, gt = image.contiguous(), gt.contiguous()
+        lut = None if lut is None else lut.contiguous()
+        _, H, W = image.shape
+        f32 = dict(dtype=torch.float32, device=image.device)
+        loss = torch.empty(1, **f32)
+        l1e, sse = errors if errors is not None else (torch.empty(H, W, **f32), torch.empty(H, W, **f32))
+        dmaps = torch.empty(3, 3, H, W, **f32)
+        scratch = torch.empty(lib.ex4d_l1_ssim_scratch_floats(H, W), **f32)
+        with _abi.stream(image.device) as stream:
+            _abi.call("ex4d_l1_ssim_forward_u8", H, W, image.data_ptr(), gt.data_ptr(), gt.shape[2], _abi.ptr(lut), float(lambda_dssim),
+                      _WINDOW.ctypes.data, loss.data_ptr(), l1e.data_ptr(), sse.data_ptr(), dmaps.data_ptr(), scratch.data_ptr(), stream)
+        ctx.lam, ctx.lut = float(lambda_dssim), lut
+        ctx.save_for_backward(image, gt, dmaps)
+        ctx.mark_non_differentiable(l1e, sse)
+        return loss.reshape(()), l1e, sse
+
+    @staticmethod
+    def backward(ctx, g_loss, _g1, _g2):
+        image, gt, dmaps = ctx.saved_tensors
+        _, H, W = image.shape
+        g = g_loss.reshape(1).to(torch.float32).contiguous()
+        grad = torch.empty_like(image)
+        with _abi.stream(image.device) as stream:
+            _abi.call("ex4d_l1_ssim_backward_u8", H, W, image.data_ptr(), gt.data_ptr(), gt.shape[2], _abi.ptr(ctx.lut), ctx.lam,
+                      _WINDOW.ctypes.data, dmaps.data_ptr(), g.data_ptr(), grad.data_ptr(), stream)
+        return grad, None, None, None, None
+
+
+def l1_ssim_loss(image, gt_image, lambda_dssim=0.2, acc=None, lut=None):
     """(loss, l1_errors[H,W], ssim_errors[H,W]) of train.py:144-151 for a [C,H,W] render and its ground truth.
     With `acc` (the rasterizer's [1,H,W] accumulation output) a fourth value is returned: the [3,H,W] tensor
     stack([acc[0], l1_errors, ssim_errors]) the reference installs as the gradient of the flow image (train.py:151-152);
-    the two error maps are then written straight into it (they are views of it)."""
+    the two error maps are then written straight into it (they are views of it).
+    A uint8 gt_image is the decoded frame [H,W,3|4]; `lut` (CPU float32 [256], default frames.gt_lut(): u / 255) gives its bytes
+    their values."""
+    if gt_image.dtype == torch.uint8:
+        op = lambda errors: _L1SSIMBytes.apply(image, gt_image, lambda_dssim, errors, lut)
+    elif lut is not None:
+        raise RuntimeError("lut= belongs to uint8 ground truth; a float gt_image already holds its values")
+    else:
+        op = lambda errors: _L1SSIM.apply(image, gt_image, lambda_dssim, errors)
     if acc is None:
-        return _L1SSIM.apply(image, gt_image, lambda_dssim, None)
+        return op(None)
     H, W = image.shape[-2:]
     hook = torch.empty(3, H, W, dtype=torch.float32, device=image.device)
     hook[0].copy_(acc.detach()[0])
-    loss, l1e, sse = _L1SSIM.apply(image, gt_image, lambda_dssim, (hook[1], hook[2]))
+    loss, l1e, sse = op((hook[1], hook[2]))
     return loss, l1e, sse, hook
 
 

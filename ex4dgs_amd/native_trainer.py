@@ -84,17 +84,29 @@ class NativeTrainer:
             raise RuntimeError(lib.ex4d_trainer_last_error().decode())
 
     def step(self, cam, bg, t, gt_image, *, l1_accum=False, stats=None, densify_stats=True, prune_stats=True, apply_optimizer=True,
-             nan_census=False):
+             nan_census=False, lut=None):
         """One iteration on the current stream (asynchronous apart from the rasterizer's instance-count read-back).
         l1_accum: the error hook of train.py:148-153 -- output('error_grad') is viewspace_l1points.grad, output('hook') the hook tensor.
         stats: a densify.DensityStats updated by this frame as DensityStats.update(radii, viewspace_grad, error_grad, t,
         densify_stats=, prune_stats=, l1_accum=) would (its blocks are looked up at every call: density control replaces them).
         apply_optimizer=False: gradients and statistics only -- the iteration train.py densifies in, whose optimizer.step() skips every
         replaced tensor; the step count does not advance.  nan_census: report() tells whether _xyz / _xyz_motion hold a NaN after the
-        step.  All defaults: the plain ex4d_trainer_step."""
+        step.  All defaults: the plain ex4d_trainer_step.
+        gt_image may be the frame as decoded: a contiguous uint8 [H,W,3|4] device tensor (frames.FrameStore.get / FrameStream.pop)
+        with lut (CPU float32 [256], frames.gt_lut(im_scale); None: u / 255) -- ex4d_trainer_step_u8, the same iteration.  The frame
+        must keep its content until the step's work on the stream is done."""
         if int(cam.image_height) != self.H or int(cam.image_width) != self.W:
             raise RuntimeError("camera size differs from the one the trainer was built for")
-        if tuple(gt_image.shape) != (3, self.H, self.W) or gt_image.dtype != torch.float32 or not gt_image.is_contiguous() or gt_image.device != self.device:
+        u8 = gt_image.dtype == torch.uint8
+        if u8:
+            if gt_image.dim() != 3 or tuple(gt_image.shape[:2]) != (self.H, self.W) or gt_image.shape[2] not in (3, 4) \
+                    or not gt_image.is_contiguous() or gt_image.device != self.device:
+                raise RuntimeError(f"uint8 gt_image must be a contiguous [{self.H},{self.W},3|4] tensor on {self.device}")
+            if lut is not None and (lut.device.type != "cpu" or lut.dtype != torch.float32 or tuple(lut.shape) != (256,) or not lut.is_contiguous()):
+                raise RuntimeError("lut must be a contiguous CPU float32 [256] tensor (frames.gt_lut)")
+        elif lut is not None:
+            raise RuntimeError("lut= belongs to uint8 ground truth; a float gt_image already holds its values")
+        elif tuple(gt_image.shape) != (3, self.H, self.W) or gt_image.dtype != torch.float32 or not gt_image.is_contiguous() or gt_image.device != self.device:
             raise RuntimeError(f"gt_image must be a contiguous float32 [3,{self.H},{self.W}] tensor on {self.device}")
         self._moments = None
         R = C.c_int32(0)
@@ -115,7 +127,9 @@ class NativeTrainer:
                                 (L1_STATS if (densify_stats and l1_accum) else 0)
                 o.stats_s, o.stats_d = _abi.ptr(stats.static), _abi.ptr(stats.dynamic)
         with _abi.stream(self.device) as stream:
-            if plain:
+            if u8:
+                _abi.call("ex4d_trainer_step_u8", *args, int(gt_image.shape[2]), _abi.ptr(lut), stream, C.byref(R), None if plain else C.byref(o))
+            elif plain:
                 _abi.call("ex4d_trainer_step", *args, stream, C.byref(R))
             else:
                 _abi.call("ex4d_trainer_step_ex", *args, stream, C.byref(R), C.byref(o))

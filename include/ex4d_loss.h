@@ -38,6 +38,20 @@ int ex4d_l1_ssim_backward(int32_t C, int32_t H, int32_t W, const float *img, con
                           const float *window /* host [11] */, const float *dmaps, const float *grad_loss /* device [1] */,
                           float *grad_img, void *stream);
 
+/* The same two calls on ground truth as an image decoder leaves it: gt is DEVICE uint8 [H,W,S] (pixel_stride S = 3 or 4 bytes per
+ * pixel, any byte alignment), channel c < 3 of pixel (y,x) is lut[gt[(y*W + x)*S + c]]; a fourth byte per pixel is never read (the
+ * reference takes [:3], scene/__init__.py:201).  lut: HOST [256] floats read during the call, as window is -- the reference's
+ * (u / 255.0 / im_scale).clamp(0, 1) or any other table; NULL = (float)u / 255.0f.  C = 3; outputs, dmaps and
+ * ex4d_l1_ssim_scratch_floats exactly as above, bit for bit what the float calls give on the looked-up [3,H,W] image.  No allocation,
+ * no copy, no synchronisation: the table travels in the kernel arguments, so the calls can be captured into a graph (which then holds
+ * the table by value). */
+int ex4d_l1_ssim_forward_u8(int32_t H, int32_t W, const float *img, const uint8_t *gt, int32_t pixel_stride,
+                            const float *lut /* host [256] or NULL */, float lambda_dssim, const float *window /* host [11] */,
+                            float *loss, float *l1_errors, float *ssim_errors, float *dmaps, float *scratch, void *stream);
+int ex4d_l1_ssim_backward_u8(int32_t H, int32_t W, const float *img, const uint8_t *gt, int32_t pixel_stride,
+                             const float *lut /* host [256] or NULL */, float lambda_dssim, const float *window /* host [11] */,
+                             const float *dmaps, const float *grad_loss /* device [1] */, float *grad_img, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,7 @@
  * with a workspace that lives across iterations -- no Python, no autograd graph, no per-iteration allocation:
  *     ex4d_attributes_forward                  (getters of scene/c_gaussian_model.py:170-215, :330-375)
  *  -> ex4d_forward_split_sh                    (render: gaussian_renderer/__init__.py:19-124, the SH tensors as the model stores them)
- *  -> ex4d_l1_ssim_forward / _backward         (train.py:144-151, utils/loss_utils.py)
+ *  -> ex4d_l1_ssim_forward / _backward         (train.py:144-151, utils/loss_utils.py; their _u8 forms in ex4d_trainer_step_u8)
  *  -> ex4d_backward_split_sh
  *  -> ex4d_attributes_backward_sliced          (keyframe gradients as the 4 / 2 touched time slices)
  *  -> ex4d_radam_step + ex4d_radam_step_sliced (scene/c_gaussian_model.py:430-449, train.py:250)
@@ -89,6 +89,13 @@ typedef struct Ex4dTrainerStepOptions {
 int ex4d_trainer_step_ex(Ex4dTrainer *t, double timestamp, const float *viewmatrix, const float *projmatrix, const float *campos,
                          const float *background, const float *gt_image, void *stream, int32_t *num_rendered,
                          const Ex4dTrainerStepOptions *opt);
+/* ex4d_trainer_step_ex against ground truth as decoded: gt_u8 is DEVICE uint8 [H,W,pixel_stride] (3 or 4 bytes per pixel, any byte
+ * alignment -- a frame of a resident store), lut the HOST table of ex4d_l1_ssim_forward_u8 (NULL = u / 255).  The same sequence with
+ * every option, report and re-run; its two loss calls are the _u8 ones, and a re-run frame reads gt_u8 again, so the frame has to
+ * stay as it is until the step's work on `stream` is done.  opt = NULL is the plain step. */
+int ex4d_trainer_step_u8(Ex4dTrainer *t, double timestamp, const float *viewmatrix, const float *projmatrix, const float *campos,
+                         const float *background, const uint8_t *gt_u8, int32_t pixel_stride, const float *lut /* host [256] or NULL */,
+                         void *stream, int32_t *num_rendered, const Ex4dTrainerStepOptions *opt);
 
 /* What a loop reads back per iteration: at the end of every ex4d_trainer_step_ex with options the loss word and the two census flags
  * are copied to pinned host memory behind an event; ex4d_trainer_report waits for that event -- the one wait that stands for
