@@ -78,6 +78,7 @@ __device__ __forceinline__ int work_item_of_block(int nwork)
     return (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
 }
 
+// (frame_metrics_kernel below repeats this kernel's fetch / commit / ring / barrier scheme: a fix to the window scheme belongs in both)
 template <typename T, typename... Table>
 __global__ __launch_bounds__(256) void l1_ssim_fwd_kernel(int C, int H, int W, const float *__restrict__ img,
     const T *__restrict__ gt, Window win, float *__restrict__ l1_errors, float *__restrict__ ssim_errors,
@@ -345,6 +346,187 @@ __global__ __launch_bounds__(256) void l1_ssim_bwd_kernel(int C, int H, int W, c
     }
 }
 
+// ---- SCORING a rendered view (ex4d_frame_metrics*): render.py:64-88 / train.py:313-362 of the reference.  The forward's rolling window
+// (same strips, segments, ring and work-item map; C = 3, one channel group) without what only training reads: no dmaps, no error maps,
+// so the column pass stores nothing.  The image value is clamped (EX4D_METRICS_CLAMP) when its row is committed to LDS, so every metric
+// and the bytes see the clamped value; squared error, non-finite count and the pixel's three bytes come from the centre tap of the
+// row pass, where the L1 term comes from.  Four float partial sums per workgroup (a workgroup has at most 48 x 64 x 3 = 9 216 values:
+// its count is exact in a float); frame_metrics_finish_kernel adds them in double and writes the row.
+static_assert(sizeof(float) * (2 * 2 * CG * RPI * (SIN + 2) + CG * 5 * RING * SW + 16 + 256) <= 80 * 1024, "frame_metrics_kernel: two workgroups per CU need <= 80 KB of LDS each, the table included");
+
+// the 8-bit value of an image value.  Default: torch's mul(255).add_(0.5).clamp_(0, 255).to(uint8) -- product and sum are rounded
+// SEPARATELY, as the two torch kernels round them (this file is compiled with contraction on: the intrinsics never fuse); trunc:
+// (clamp(x, 0, 1) * 255).byte().  A NaN fails every comparison and gives 0 (this library's choice: torch leaves it unspecified).
+__device__ __forceinline__ uint8_t metrics_byte(float x, bool trunc)
+{
+    float t;
+    if (trunc) t = __fmul_rn(x < 0.f ? 0.f : (x > 1.f ? 1.f : x), 255.f);
+    else t = __fadd_rn(__fmul_rn(x, 255.f), 0.5f);
+    return !(t > 0.f) ? (uint8_t)0 : (t >= 255.f ? (uint8_t)255 : (uint8_t)(int)t);
+}
+
+template <typename T, typename... Table>
+__global__ __launch_bounds__(256) void frame_metrics_kernel(int H, int W, const float *__restrict__ img, const T *__restrict__ gt,
+    Window win, int flags, uint8_t *__restrict__ out_u8, float *__restrict__ partials, int nsx, int nsy, Table... table)
+{
+    constexpr bool kBytes = sizeof...(Table) != 0;
+    __shared__ float s_in[2][2][CG][RPI][SIN + 2];      // [buffer][x | y][channel][row][column]
+    __shared__ float s_ring[CG][5][RING][SW];           // row-pass results of the last RING image rows
+    __shared__ float s_red[4][4];
+    const PixelLds px8 = table_to_lds(table...);        // (published by the barrier in front of the first fetch)
+    const int nwork = nsx * nsy;
+    const int wi = work_item_of_block(nwork);
+    const int col = threadIdx.x & (SW - 1), rsub = threadIdx.x >> 6;
+    const size_t HW = (size_t)H * W;
+    const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
+    const bool clamp01 = (flags & EX4D_METRICS_CLAMP) != 0, trunc = (flags & EX4D_METRICS_QUANT_TRUNC) != 0;
+    float l1_total = 0.f, sq_total = 0.f, ssim_total = 0.f, bad_total = 0.f;
+    if (wi < nwork) {
+        const int x0 = (wi % nsx) * SW, y0 = (wi / nsx) * SEG;
+        const int rows_out = (H - y0) < SEG ? (H - y0) : SEG;
+        const int n_in = rows_out + 2 * LH;              // image rows y0 - 5 .. y0 + rows_out + 4
+        const int n_it = (n_in + RPI - 1) / RPI;
+        const int px = x0 + col;
+        const int hrow = (int)threadIdx.x / (2 * LH), hcol = SW + (int)threadIdx.x % (2 * LH);
+        const bool has_halo = threadIdx.x < RPI * 2 * LH;
+        float rm[2 * CG], rh[2 * CG];
+        auto fetch = [&](int it) {
+            const int ym = y0 - LH + it * RPI + rsub, xm = x0 - LH + col;
+            const int yh = y0 - LH + it * RPI + hrow, xh = x0 - LH + hcol;
+            const bool okm = xm >= 0 && xm < W && ym >= 0 && ym < H, okh = has_halo && xh >= 0 && xh < W && yh >= 0 && yh < H;
+            const size_t om = (size_t)ym * W + xm, oh = (size_t)yh * W + xh;
+#pragma unroll
+            for (int pl = 0; pl < 2 * CG; pl++) {
+                const int ch = pl % CG;
+                if constexpr (kBytes) {
+                    if (pl / CG) {                       // the BYTE stays in flight; commit looks it up
+                        rm[pl] = byte_bits(okm, gt, om * px8.S + ch);
+                        rh[pl] = byte_bits(okh, gt, oh * px8.S + ch);
+                        continue;
+                    }
+                }
+                const float *src = ((pl / CG) ? (const float *)gt : img) + (size_t)ch * HW;
+                rm[pl] = okm ? src[om] : 0.f;            // zero padding (conv2d padding=5)
+                rh[pl] = okh ? src[oh] : 0.f;
+            }
+        };
+        auto commit = [&](int buf) {
+#pragma unroll
+            for (int pl = 0; pl < 2 * CG; pl++) {
+                float vm = rm[pl], vh = rh[pl];
+                if (pl / CG) {
+                    if constexpr (kBytes) { vm = byte_value(vm, px8.v); vh = byte_value(vh, px8.v); }
+                } else if (clamp01) {                    // torch.clamp: a NaN stays a NaN (the padding's 0 stays 0)
+                    vm = vm < 0.f ? 0.f : (vm > 1.f ? 1.f : vm);
+                    vh = vh < 0.f ? 0.f : (vh > 1.f ? 1.f : vh);
+                }
+                s_in[buf][pl / CG][pl % CG][rsub][col] = vm;
+                if (has_halo) s_in[buf][pl / CG][pl % CG][hrow][hcol] = vh;
+            }
+        };
+        __syncthreads();                                 // (the table)
+        fetch(0);
+        commit(0);
+        __syncthreads();
+        for (int it = 0; it < n_it; it++) {
+            const int buf = it & 1;
+            if (it + 1 < n_it) fetch(it + 1);            // in flight while this iteration's rows are convolved
+            // ---- row pass of image row rin (relative to y0 - 5) -> ring; when the row lies inside the segment its pixels are output
+            // pixels: their L1 and squared-error terms, their non-finite count and their bytes
+            const int rin = it * RPI + rsub;
+            if (rin < n_in) {
+                const int ro = rin - LH;
+                const bool is_out = ro >= 0 && ro < rows_out && px < W;
+                uint8_t *o8 = (is_out && out_u8) ? out_u8 + ((size_t)(y0 + ro) * W + px) * 3 : nullptr;
+                float l1 = 0.f, sq = 0.f, bad = 0.f;
+#pragma unroll 1
+                for (int ch = 0; ch < CG; ch++) {
+                    const float *sx = &s_in[buf][0][ch][rsub][col], *sy = &s_in[buf][1][ch][rsub][col];
+                    float m1 = 0.f, m2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
+#pragma unroll
+                    for (int k = 0; k < EX4D_SSIM_WINDOW; k++) {
+                        const float a = sx[k], b = sy[k], wk = win.w[k];
+                        m1 += wk * a; m2 += wk * b; e11 += wk * (a * a); e22 += wk * (b * b); e12 += wk * (a * b);
+                    }
+                    const int slot = rin & (RING - 1);
+                    s_ring[ch][0][slot][col] = m1; s_ring[ch][1][slot][col] = m2; s_ring[ch][2][slot][col] = e11;
+                    s_ring[ch][3][slot][col] = e22; s_ring[ch][4][slot][col] = e12;
+                    const float x = sx[LH], d = x - sy[LH];
+                    l1 += fabsf(d);
+                    sq += d * d;
+                    bad += fabsf(x) <= 3.402823466e+38f ? 0.f : 1.f;          // NaN or +-inf
+                    if (o8) o8[ch] = metrics_byte(x, trunc);
+                }
+                if (is_out) { l1_total += l1; sq_total += sq; bad_total += bad; }
+            }
+            __syncthreads();
+            // ---- column pass of output row ro: its window (image rows ro .. ro + 10 relative to y0 - 5) is complete
+            const int ro = it * RPI + rsub - 2 * LH;
+            if (ro >= 0 && ro < rows_out && px < W) {
+                float ssim = 0.f;
+#pragma unroll 1
+                for (int ch = 0; ch < CG; ch++) {
+                    float mu1 = 0.f, mu2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
+#pragma unroll
+                    for (int k = 0; k < EX4D_SSIM_WINDOW; k++) {
+                        const float wk = win.w[k];
+                        const int slot = (ro + k) & (RING - 1);
+                        mu1 += wk * s_ring[ch][0][slot][col]; mu2 += wk * s_ring[ch][1][slot][col];
+                        e11 += wk * s_ring[ch][2][slot][col]; e22 += wk * s_ring[ch][3][slot][col]; e12 += wk * s_ring[ch][4][slot][col];
+                    }
+                    // utils/loss_utils.py:61-74, in the forward's order of operations
+                    const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
+                    const float s1 = e11 - mu1_sq, s2 = e22 - mu2_sq, s12 = e12 - mu12;
+                    const float a1 = 2.f * mu12 + C1, a2 = 2.f * s12 + C2, b1 = mu1_sq + mu2_sq + C1, b2 = s1 + s2 + C2;
+                    const float inv = 1.f / (b1 * b2);
+                    ssim += (a1 * a2) * inv;
+                }
+                ssim_total += ssim;
+            }
+            if (it + 1 < n_it) commit(buf ^ 1);
+            __syncthreads();
+        }
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        l1_total += __shfl_xor(l1_total, o, 64); sq_total += __shfl_xor(sq_total, o, 64);
+        ssim_total += __shfl_xor(ssim_total, o, 64); bad_total += __shfl_xor(bad_total, o, 64);
+    }
+    if (lane == 0) { s_red[0][wave] = l1_total; s_red[1][wave] = sq_total; s_red[2][wave] = ssim_total; s_red[3][wave] = bad_total; }
+    __syncthreads();
+    if (threadIdx.x < 4)
+        partials[4 * blockIdx.x + threadIdx.x] = s_red[threadIdx.x][0] + s_red[threadIdx.x][1] + s_red[threadIdx.x][2] + s_red[threadIdx.x][3];
+}
+
+__global__ __launch_bounds__(256) void frame_metrics_finish_kernel(int nblocks, const float *__restrict__ partials, double inv_count,
+    double *__restrict__ row)
+{
+    __shared__ double s[4][4];
+    double a[4] = { 0.0, 0.0, 0.0, 0.0 };
+    for (int i = threadIdx.x; i < nblocks; i += 256) {
+#pragma unroll
+        for (int q = 0; q < 4; q++) a[q] += (double)partials[4 * i + q];
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) a[q] += __shfl_xor(a[q], o, 64);
+        if (lane == 0) s[q][wave] = a[q];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double mse = (s[1][0] + s[1][1] + s[1][2] + s[1][3]) * inv_count;
+        row[0] = (s[0][0] + s[0][1] + s[0][2] + s[0][3]) * inv_count;
+        row[1] = mse;
+        row[2] = 20.0 * log10(1.0 / sqrt(mse));                               // utils/image_utils.py:17-19; +inf at mse 0
+        row[3] = (s[2][0] + s[2][1] + s[2][2] + s[2][3]) * inv_count;
+        row[4] = s[3][0] + s[3][1] + s[3][2] + s[3][3];
+        row[5] = row[6] = row[7] = 0.0;
+    }
+}
+
 thread_local char g_loss_err[256] = "";
 
 bool check_args(int C, int H, int W, const void *a, const void *b, const float *window)
@@ -399,6 +581,28 @@ bool pixels_of(const uint8_t *gt, int32_t pixel_stride, const float *lut, PixelT
     return true;
 }
 
+template <typename T, typename... Table>
+int launch_metrics(int H, int W, const float *img, const T *gt, const float *window, int flags, uint8_t *out_u8, double *row,
+                   float *scratch, hipStream_t stream, const Table &... table)
+{
+    Window win;
+    for (int i = 0; i < EX4D_SSIM_WINDOW; i++) win.w[i] = window[i];
+    const int nblocks = blocks_of(H, W);
+    hipLaunchKernelGGL((frame_metrics_kernel<T, Table...>), dim3(nblocks), dim3(256), 0, stream, H, W, img, gt, win, flags, out_u8, scratch,
+                       strips_of(W), segments_of(H), table...);
+    hipLaunchKernelGGL(frame_metrics_finish_kernel, dim3(1), dim3(256), 0, stream, nblocks, scratch, 1.0 / (3.0 * H * W), row);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { snprintf(g_loss_err, sizeof(g_loss_err), "launch failed: %s", hipGetErrorString(e)); return EX4D_ERR_HIP; }
+    return EX4D_OK;
+}
+
+bool check_metrics_args(int H, int W, const void *img, const void *gt, const float *window, int flags, const double *row, const float *scratch)
+{
+    if (!check_args(3, H, W, img, gt, window) || !row || !scratch) { snprintf(g_loss_err, sizeof(g_loss_err), "bad argument"); return false; }
+    if (flags & ~(EX4D_METRICS_CLAMP | EX4D_METRICS_QUANT_TRUNC)) { snprintf(g_loss_err, sizeof(g_loss_err), "flags %d: EX4D_METRICS_CLAMP | EX4D_METRICS_QUANT_TRUNC only", flags); return false; }
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -443,6 +647,26 @@ int ex4d_l1_ssim_backward_u8(int32_t H, int32_t W, const float *img, const uint8
     if (!check_args(3, H, W, img, gt, window) || !dmaps || !grad_loss || !grad_img) { snprintf(g_loss_err, sizeof(g_loss_err), "bad argument"); return EX4D_ERR_ARG; }
     if (!pixels_of(gt, pixel_stride, lut, &px)) return EX4D_ERR_ARG;
     return launch_backward(3, H, W, img, gt, lambda_dssim, window, dmaps, grad_loss, grad_img, (hipStream_t)stream_, px);
+}
+
+size_t ex4d_frame_metrics_scratch_floats(int32_t H, int32_t W) { return 4 * (size_t)blocks_of(H, W) + 64; }
+
+int ex4d_frame_metrics(int32_t H, int32_t W, const float *img, const float *gt, const float *window, int32_t flags, uint8_t *out_u8,
+                       double *row, float *scratch, void *stream_)
+{
+    g_loss_err[0] = 0;
+    if (!check_metrics_args(H, W, img, gt, window, flags, row, scratch)) return EX4D_ERR_ARG;
+    return launch_metrics(H, W, img, gt, window, flags, out_u8, row, scratch, (hipStream_t)stream_);
+}
+
+int ex4d_frame_metrics_u8(int32_t H, int32_t W, const float *img, const uint8_t *gt, int32_t pixel_stride, const float *lut,
+                          const float *window, int32_t flags, uint8_t *out_u8, double *row, float *scratch, void *stream_)
+{
+    g_loss_err[0] = 0;
+    PixelTable px;
+    if (!check_metrics_args(H, W, img, gt, window, flags, row, scratch)) return EX4D_ERR_ARG;
+    if (!pixels_of(gt, pixel_stride, lut, &px)) return EX4D_ERR_ARG;
+    return launch_metrics(H, W, img, gt, window, flags, out_u8, row, scratch, (hipStream_t)stream_, px);
 }
 
 }  // extern "C"

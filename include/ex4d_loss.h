@@ -52,6 +52,30 @@ int ex4d_l1_ssim_backward_u8(int32_t H, int32_t W, const float *img, const uint8
                              const float *lut /* host [256] or NULL */, float lambda_dssim, const float *window /* host [11] */,
                              const float *dmaps, const float *grad_loss /* device [1] */, float *grad_img, void *stream);
 
+/* SCORING a rendered view (render.py:64-88, train.py:313-362 of the reference): one pass over a float32 [3,H,W] image and its ground
+ * truth -- float32 [3,H,W], or uint8 [H,W,S] through lut exactly as above -- gives the L1, the MSE, the PSNR of
+ * utils/image_utils.py:17-19 and the mean of the SSIM map of loss_utils.py:47-81, and optionally the image as 8-bit pixels.  No
+ * derivative maps, no error maps.  row: DEVICE double[8], all eight written on every call:
+ *     row[0] mean|x - y|   row[1] mean (x - y)^2   row[2] 20 log10(1 / sqrt(row[1])) (+inf at MSE 0, as torch gives)
+ *     row[3] mean of the SSIM map   row[4] number of non-finite image values (exact)   row[5..7] 0
+ * where x is the image value AS SCORED: with EX4D_METRICS_CLAMP, clamp(v, 0, 1) (train.py:342; NaN stays NaN, +-inf become 1 / 0 and
+ * are then no longer counted in row[4]).  The sums are float per workgroup and double across workgroups.
+ * out_u8: DEVICE uint8 [H,W,3] (any byte alignment) or NULL.  Default bytes: (uint8)clamp(x * 255 + 0.5, 0, 255), the product and the
+ * sum rounded separately as torch's mul and add are (torchvision's save_image, render.py:75); with EX4D_METRICS_QUANT_TRUNC:
+ * (uint8)(clamp(x, 0, 1) * 255) (train.py:101).  +inf gives 255, -inf gives 0.  A NaN gives 0: torch leaves that conversion
+ * unspecified, 0 is this library's choice.
+ * scratch: ex4d_frame_metrics_scratch_floats(H, W) floats.  window and lut are HOST arrays read during the call.  No allocation, no
+ * copy, no synchronisation: the calls can be captured into a graph.  C is 3 only: render.py scores RGB. */
+#define EX4D_METRICS_CLAMP 1
+#define EX4D_METRICS_QUANT_TRUNC 2
+size_t ex4d_frame_metrics_scratch_floats(int32_t H, int32_t W);
+int ex4d_frame_metrics(int32_t H, int32_t W, const float *img, const float *gt, const float *window /* host [11] */,
+                       int32_t flags, uint8_t *out_u8 /* [H,W,3] or NULL */, double *row /* device [8] */, float *scratch,
+                       void *stream);
+int ex4d_frame_metrics_u8(int32_t H, int32_t W, const float *img, const uint8_t *gt, int32_t pixel_stride,
+                          const float *lut /* host [256] or NULL */, const float *window /* host [11] */, int32_t flags,
+                          uint8_t *out_u8 /* [H,W,3] or NULL */, double *row /* device [8] */, float *scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
