@@ -176,7 +176,10 @@ PROTOTYPES = {
         _status("ex4d_l1_ssim_backward_u8", i32, i32, vp, vp, i32, vp, f32, *[vp] * 5),
         _value("ex4d_frame_metrics_scratch_floats", size, i32, i32),
         _status("ex4d_frame_metrics", i32, i32, vp, vp, vp, i32, *[vp] * 4),
-        _status("ex4d_frame_metrics_u8", i32, i32, vp, vp, i32, vp, vp, i32, *[vp] * 4))),
+        _status("ex4d_frame_metrics_u8", i32, i32, vp, vp, i32, vp, vp, i32, *[vp] * 4),
+        _value("ex4d_frame_skssim_scratch_floats", size, i32, i32),
+        _status("ex4d_frame_skssim", i32, i32, vp, vp, i32, *[vp] * 3),
+        _status("ex4d_frame_skssim_u8", i32, i32, vp, vp, i32, vp, i32, *[vp] * 3))),
     "ex4d_optim.h": ("ex4d_optim_last_error", (
         _value("ex4d_optim_last_error", text),
         _status("ex4d_radam_step", P(Ex4dRadamTensor), i32, f64, f64, f64, vp),

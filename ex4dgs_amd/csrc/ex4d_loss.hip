@@ -527,6 +527,207 @@ __global__ __launch_bounds__(256) void frame_metrics_finish_kernel(int nblocks, 
     }
 }
 
+// ---- scikit-image's SSIM of a rendered view (ex4d_frame_skssim*): render.py:78-79 of the reference,
+//     sk_ssim(render, gt, data_range=R, multichannel=True, channel_axis=0),   R = 1 (SKSSIM) and R = 2 (SKSSIM2)
+// on float32 [3,H,W] arrays, read as current scikit-image (0.22 and later) reads it: `multichannel` falls into **kwargs and is ignored,
+// channel_axis=0 holds.  (Earlier releases either override channel_axis with -1 or ignore it; on a [3,H,W] array both fail with
+// "win_size exceeds image extent", so there is no other working reading.)  Per channel: the 7x7 uniform means ux, uy, uxx, uyy, uxy of
+// X, Y, XX, YY, XY; the sample covariances v = (49/48)(uxx - ux^2) ...; C1 = (0.01 R)^2, C2 = (0.03 R)^2;
+// S = (2 ux uy + C1)(2 vxy + C2) / ((ux^2 + uy^2 + C1)(vx + vy + C2)); the mean of S over the positions whose window lies wholly inside
+// the image (scikit-image crops 3 pixels per side: the border mode never matters); the mean of the three channel means.
+// The rolling window of frame_metrics_kernel (strips, segments, ring, double-buffered fetch / commit, work-item map, byte lookup, clamp
+// at commit) with three differences.  Strips and segments tile the OUTPUT domain (H-6) x (W-6): output (oy, ox) reads image rows
+// oy .. oy+6 and columns ox .. ox+6, all inside the image -- no zero padding (the zeros a fetch beyond the image leaves feed masked
+// outputs only).  The 7 equal taps are added directly in a fixed order, in both passes: a sum depends on the image position alone,
+// never on where a strip or segment starts.  The second moments are CENTRED, not raw: the row pass keeps, per 7-pixel row of a
+// window, the two row means mx, my and the sums A, B, C of (x-mx)^2, (y-my)^2, (x-mx)(y-my); the column pass combines the seven rows as
+// the pairwise variance update does: ux = mean(mx), sum (x-ux)^2 = sum A + 7 sum (mx-ux)^2, likewise for y and xy, and v = that / 48.
+// The same five window quantities as ux, uy, uxx, uyy, uxy, without the cancellation of uxx - ux^2: raw float32 sums of 49 products
+// miss the 1e-6 bar on a low-variance pair (2e-6 where the ground truth is piecewise constant and the render adds noise of sigma
+// 0.002: the accumulated rounding of sums near 40 against C2 = 9e-4), the centred ones are within 1e-9 there.  Every product is an
+// explicit fmaf / __fmul_rn, so the x, y and xy terms of equal images are equal bits; both S come from the same five quantities;
+// numerator and denominator are formed by the same float operations in the same order and divided with a correctly rounded division,
+// so equal images score exactly 1.  Three float partial sums per workgroup: sum S(R=1), sum S(R=2), the count of positions whose
+// S(R=1) is not finite (at most 48 x 64 x 3: exact).
+#define SKH 3                       // window half width
+#define SKIN (SW + 2 * SKH)         // 70 input columns of a strip
+#define SKRING 16                   // ring rows (>= EX4D_SKSSIM_WINDOW + RPI - 1, power of two)
+static_assert(EX4D_SKSSIM_WINDOW == 2 * SKH + 1 && SKRING >= EX4D_SKSSIM_WINDOW + RPI - 1 && (SKRING & (SKRING - 1)) == 0, "frame_skssim_kernel: the ring holds a window and an iteration");
+static_assert(RPI * 2 * SKH <= 256, "frame_skssim_kernel: one halo load per thread");
+static_assert(sizeof(float) * (2 * 2 * CG * RPI * (SKIN + 2) + CG * 5 * SKRING * SW + 12 + 256) <= 80 * 1024, "frame_skssim_kernel: two workgroups per CU need <= 80 KB of LDS each, the table included");
+
+// seven taps of a window, m = their mean, (A, B, C) = the sums of dx^2, dy^2, dx dy about the means (fixed order, explicit rounding)
+__device__ __forceinline__ void sk_centred(const float (&a)[EX4D_SKSSIM_WINDOW], const float (&b)[EX4D_SKSSIM_WINDOW], float &ma, float &mb,
+                                           float &A, float &B, float &C)
+{
+    float sa = a[0], sb = b[0];
+#pragma unroll
+    for (int k = 1; k < EX4D_SKSSIM_WINDOW; k++) { sa = __fadd_rn(sa, a[k]); sb = __fadd_rn(sb, b[k]); }
+    ma = __fmul_rn(sa, 1.0f / 7.0f); mb = __fmul_rn(sb, 1.0f / 7.0f);
+    A = B = C = 0.f;
+#pragma unroll
+    for (int k = 0; k < EX4D_SKSSIM_WINDOW; k++) {
+        const float da = __fsub_rn(a[k], ma), db = __fsub_rn(b[k], mb);
+        A = fmaf(da, da, A); B = fmaf(db, db, B); C = fmaf(da, db, C);
+    }
+}
+
+// S for one data range from the five means' derived terms: 2 ux uy, ux^2 + uy^2, 2 vxy, vx + vy
+__device__ __forceinline__ float sk_s(float m2xy, float mxxyy, float v2xy, float vxxyy, float C1, float C2)
+{
+    return __fdiv_rn(__fmul_rn(__fadd_rn(m2xy, C1), __fadd_rn(v2xy, C2)), __fmul_rn(__fadd_rn(mxxyy, C1), __fadd_rn(vxxyy, C2)));
+}
+
+template <typename T, typename... Table>
+__global__ __launch_bounds__(256) void frame_skssim_kernel(int H, int W, const float *__restrict__ img, const T *__restrict__ gt,
+    int flags, float *__restrict__ partials, int nsx, int nsy, Table... table)
+{
+    constexpr bool kBytes = sizeof...(Table) != 0;
+    __shared__ float s_in[2][2][CG][RPI][SKIN + 2];     // [buffer][x | y][channel][row][column]
+    __shared__ float s_ring[CG][5][SKRING][SW];         // row-pass results (mx, my, A, B, C) of the last SKRING image rows
+    __shared__ float s_red[3][4];
+    const PixelLds px8 = table_to_lds(table...);        // (published by the barrier in front of the first fetch)
+    const int nwork = nsx * nsy;
+    const int wi = work_item_of_block(nwork);
+    const int col = threadIdx.x & (SW - 1), rsub = threadIdx.x >> 6;
+    const size_t HW = (size_t)H * W;
+    const int Ho = H - 2 * SKH, Wo = W - 2 * SKH;       // the output domain
+    const bool clamp01 = (flags & EX4D_METRICS_CLAMP) != 0;
+    const float inv_nm1 = 1.0f / 48.0f;                  // sample covariance (scikit-image's default): / (49 - 1)
+    float s1_total = 0.f, s2_total = 0.f, bad_total = 0.f;
+    if (wi < nwork) {
+        const int x0 = (wi % nsx) * SW, y0 = (wi / nsx) * SEG;           // first output column / row = first image column / row read
+        const int rows_out = (Ho - y0) < SEG ? (Ho - y0) : SEG;
+        const int n_in = rows_out + 2 * SKH;             // image rows y0 .. y0 + rows_out + 5
+        const int n_it = (n_in + RPI - 1) / RPI;
+        const int px = x0 + col;                         // this thread's output column
+        const int hrow = (int)threadIdx.x / (2 * SKH), hcol = SW + (int)threadIdx.x % (2 * SKH);
+        const bool has_halo = threadIdx.x < RPI * 2 * SKH;
+        float rm[2 * CG], rh[2 * CG];
+        auto fetch = [&](int it) {
+            const int ym = y0 + it * RPI + rsub, xm = x0 + col;
+            const int yh = y0 + it * RPI + hrow, xh = x0 + hcol;
+            const bool okm = xm < W && ym < H, okh = has_halo && xh < W && yh < H;
+            const size_t om = (size_t)ym * W + xm, oh = (size_t)yh * W + xh;
+#pragma unroll
+            for (int pl = 0; pl < 2 * CG; pl++) {
+                const int ch = pl % CG;
+                if constexpr (kBytes) {
+                    if (pl / CG) {                       // the BYTE stays in flight; commit looks it up
+                        rm[pl] = byte_bits(okm, gt, om * px8.S + ch);
+                        rh[pl] = byte_bits(okh, gt, oh * px8.S + ch);
+                        continue;
+                    }
+                }
+                const float *src = ((pl / CG) ? (const float *)gt : img) + (size_t)ch * HW;
+                rm[pl] = okm ? src[om] : 0.f;            // (beyond the image: read by masked outputs only)
+                rh[pl] = okh ? src[oh] : 0.f;
+            }
+        };
+        auto commit = [&](int buf) {
+#pragma unroll
+            for (int pl = 0; pl < 2 * CG; pl++) {
+                float vm = rm[pl], vh = rh[pl];
+                if (pl / CG) {
+                    if constexpr (kBytes) { vm = byte_value(vm, px8.v); vh = byte_value(vh, px8.v); }
+                } else if (clamp01) {                    // torch.clamp: a NaN stays a NaN
+                    vm = vm < 0.f ? 0.f : (vm > 1.f ? 1.f : vm);
+                    vh = vh < 0.f ? 0.f : (vh > 1.f ? 1.f : vh);
+                }
+                s_in[buf][pl / CG][pl % CG][rsub][col] = vm;
+                if (has_halo) s_in[buf][pl / CG][pl % CG][hrow][hcol] = vh;
+            }
+        };
+        __syncthreads();                                 // (the table)
+        fetch(0);
+        commit(0);
+        __syncthreads();
+        for (int it = 0; it < n_it; it++) {
+            const int buf = it & 1;
+            if (it + 1 < n_it) fetch(it + 1);            // in flight while this iteration's rows are summed
+            // ---- row pass of image row rin (relative to y0): means and centred sums of columns px .. px + 6 -> ring
+            const int rin = it * RPI + rsub;
+            if (rin < n_in) {
+                const int slot = rin & (SKRING - 1);
+#pragma unroll 1
+                for (int ch = 0; ch < CG; ch++) {
+                    const float *sx = &s_in[buf][0][ch][rsub][col], *sy = &s_in[buf][1][ch][rsub][col];
+                    float a[EX4D_SKSSIM_WINDOW], b[EX4D_SKSSIM_WINDOW], m1, m2, e11, e22, e12;
+#pragma unroll
+                    for (int k = 0; k < EX4D_SKSSIM_WINDOW; k++) { a[k] = sx[k]; b[k] = sy[k]; }
+                    sk_centred(a, b, m1, m2, e11, e22, e12);
+                    s_ring[ch][0][slot][col] = m1; s_ring[ch][1][slot][col] = m2; s_ring[ch][2][slot][col] = e11;
+                    s_ring[ch][3][slot][col] = e22; s_ring[ch][4][slot][col] = e12;
+                }
+            }
+            __syncthreads();
+            // ---- column pass of output row ro: its window (image rows ro .. ro + 6 relative to y0) is complete
+            const int ro = it * RPI + rsub - 2 * SKH;
+            if (ro >= 0 && ro < rows_out && px < Wo) {
+#pragma unroll 1
+                for (int ch = 0; ch < CG; ch++) {
+                    float a[EX4D_SKSSIM_WINDOW], b[EX4D_SKSSIM_WINDOW], ux, uy, dxx, dyy, dxy;
+                    float sxx = 0.f, syy = 0.f, sxy = 0.f;             // (the first add is exact)
+#pragma unroll
+                    for (int k = 0; k < EX4D_SKSSIM_WINDOW; k++) {
+                        const int slot = (ro + k) & (SKRING - 1);
+                        a[k] = s_ring[ch][0][slot][col]; b[k] = s_ring[ch][1][slot][col];
+                        sxx = __fadd_rn(sxx, s_ring[ch][2][slot][col]); syy = __fadd_rn(syy, s_ring[ch][3][slot][col]);
+                        sxy = __fadd_rn(sxy, s_ring[ch][4][slot][col]);
+                    }
+                    sk_centred(a, b, ux, uy, dxx, dyy, dxy);          // the seven row means about the window's mean
+                    const float vx = __fmul_rn(fmaf(7.0f, dxx, sxx), inv_nm1), vy = __fmul_rn(fmaf(7.0f, dyy, syy), inv_nm1);
+                    const float vxy = __fmul_rn(fmaf(7.0f, dxy, sxy), inv_nm1);
+                    const float mxx = __fmul_rn(ux, ux), myy = __fmul_rn(uy, uy), mxy = __fmul_rn(ux, uy);
+                    const float m2xy = __fadd_rn(mxy, mxy), mxxyy = __fadd_rn(mxx, myy), v2xy = __fadd_rn(vxy, vxy), vxxyy = __fadd_rn(vx, vy);
+                    const float S1 = sk_s(m2xy, mxxyy, v2xy, vxxyy, 1e-4f, 9e-4f);           // data_range 1: (0.01)^2, (0.03)^2
+                    const float S2 = sk_s(m2xy, mxxyy, v2xy, vxxyy, 4e-4f, 3.6e-3f);         // data_range 2: (0.02)^2, (0.06)^2
+                    s1_total += S1; s2_total += S2;
+                    bad_total += fabsf(S1) <= 3.402823466e+38f ? 0.f : 1.f;                  // NaN or +-inf
+                }
+            }
+            if (it + 1 < n_it) commit(buf ^ 1);
+            __syncthreads();
+        }
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        s1_total += __shfl_xor(s1_total, o, 64); s2_total += __shfl_xor(s2_total, o, 64); bad_total += __shfl_xor(bad_total, o, 64);
+    }
+    if (lane == 0) { s_red[0][wave] = s1_total; s_red[1][wave] = s2_total; s_red[2][wave] = bad_total; }
+    __syncthreads();
+    if (threadIdx.x < 3)
+        partials[3 * blockIdx.x + threadIdx.x] = s_red[threadIdx.x][0] + s_red[threadIdx.x][1] + s_red[threadIdx.x][2] + s_red[threadIdx.x][3];
+}
+
+// count: 3 (H-6)(W-6), the same for every channel, so the mean of the channel means is the overall mean; divided, not multiplied by a
+// reciprocal: a sum of exact ones gives exactly 1
+__global__ __launch_bounds__(256) void frame_skssim_finish_kernel(int nblocks, const float *__restrict__ partials, double count,
+    double *__restrict__ row)
+{
+    __shared__ double s[3][4];
+    double a[3] = { 0.0, 0.0, 0.0 };
+    for (int i = threadIdx.x; i < nblocks; i += 256) {
+#pragma unroll
+        for (int q = 0; q < 3; q++) a[q] += (double)partials[3 * i + q];
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int q = 0; q < 3; q++) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) a[q] += __shfl_xor(a[q], o, 64);
+        if (lane == 0) s[q][wave] = a[q];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        row[0] = (s[0][0] + s[0][1] + s[0][2] + s[0][3]) / count;
+        row[1] = (s[1][0] + s[1][1] + s[1][2] + s[1][3]) / count;
+        row[2] = s[2][0] + s[2][1] + s[2][2] + s[2][3];
+        row[3] = 0.0;
+    }
+}
+
 thread_local char g_loss_err[256] = "";
 
 bool check_args(int C, int H, int W, const void *a, const void *b, const float *window)
@@ -603,6 +804,32 @@ bool check_metrics_args(int H, int W, const void *img, const void *gt, const flo
     return true;
 }
 
+// scikit-image's SSIM: strips and segments of the output domain (H-6) x (W-6)
+static inline int sk_blocks_of(int H, int W) { return blocks_of(H - 2 * SKH, W - 2 * SKH); }
+
+template <typename T, typename... Table>
+int launch_skssim(int H, int W, const float *img, const T *gt, int flags, double *row, float *scratch, hipStream_t stream, const Table &... table)
+{
+    const int Ho = H - 2 * SKH, Wo = W - 2 * SKH, nblocks = sk_blocks_of(H, W);
+    hipLaunchKernelGGL((frame_skssim_kernel<T, Table...>), dim3(nblocks), dim3(256), 0, stream, H, W, img, gt, flags, scratch,
+                       strips_of(Wo), segments_of(Ho), table...);
+    hipLaunchKernelGGL(frame_skssim_finish_kernel, dim3(1), dim3(256), 0, stream, nblocks, scratch, 3.0 * Ho * Wo, row);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { snprintf(g_loss_err, sizeof(g_loss_err), "launch failed: %s", hipGetErrorString(e)); return EX4D_ERR_HIP; }
+    return EX4D_OK;
+}
+
+bool check_skssim_args(int H, int W, const void *img, const void *gt, int flags, const double *row, const float *scratch)
+{
+    if (!img || !gt || !row || !scratch) { snprintf(g_loss_err, sizeof(g_loss_err), "bad argument"); return false; }
+    if (H < EX4D_SKSSIM_WINDOW || W < EX4D_SKSSIM_WINDOW) {
+        snprintf(g_loss_err, sizeof(g_loss_err), "image %d x %d: win_size exceeds image extent (H, W >= %d)", H, W, EX4D_SKSSIM_WINDOW);
+        return false;
+    }
+    if (flags & ~EX4D_METRICS_CLAMP) { snprintf(g_loss_err, sizeof(g_loss_err), "flags %d: EX4D_METRICS_CLAMP only", flags); return false; }
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -667,6 +894,28 @@ int ex4d_frame_metrics_u8(int32_t H, int32_t W, const float *img, const uint8_t 
     if (!check_metrics_args(H, W, img, gt, window, flags, row, scratch)) return EX4D_ERR_ARG;
     if (!pixels_of(gt, pixel_stride, lut, &px)) return EX4D_ERR_ARG;
     return launch_metrics(H, W, img, gt, window, flags, out_u8, row, scratch, (hipStream_t)stream_, px);
+}
+
+size_t ex4d_frame_skssim_scratch_floats(int32_t H, int32_t W)
+{
+    return (H < EX4D_SKSSIM_WINDOW || W < EX4D_SKSSIM_WINDOW) ? 0 : 3 * (size_t)sk_blocks_of(H, W) + 64;
+}
+
+int ex4d_frame_skssim(int32_t H, int32_t W, const float *img, const float *gt, int32_t flags, double *row, float *scratch, void *stream_)
+{
+    g_loss_err[0] = 0;
+    if (!check_skssim_args(H, W, img, gt, flags, row, scratch)) return EX4D_ERR_ARG;
+    return launch_skssim(H, W, img, gt, flags, row, scratch, (hipStream_t)stream_);
+}
+
+int ex4d_frame_skssim_u8(int32_t H, int32_t W, const float *img, const uint8_t *gt, int32_t pixel_stride, const float *lut,
+                         int32_t flags, double *row, float *scratch, void *stream_)
+{
+    g_loss_err[0] = 0;
+    PixelTable px;
+    if (!check_skssim_args(H, W, img, gt, flags, row, scratch)) return EX4D_ERR_ARG;
+    if (!pixels_of(gt, pixel_stride, lut, &px)) return EX4D_ERR_ARG;
+    return launch_skssim(H, W, img, gt, flags, row, scratch, (hipStream_t)stream_, px);
 }
 
 }  // extern "C"

@@ -76,6 +76,27 @@ int ex4d_frame_metrics_u8(int32_t H, int32_t W, const float *img, const uint8_t 
                           const float *lut /* host [256] or NULL */, const float *window /* host [11] */, int32_t flags,
                           uint8_t *out_u8 /* [H,W,3] or NULL */, double *row /* device [8] */, float *scratch, void *stream);
 
+/* scikit-image's SSIM of a rendered view: the SKSSIM and SKSSIM2 entries of render.py:78-79,
+ *     sk_ssim(render, gt, data_range=R, multichannel=True, channel_axis=0)   with R = 1 and R = 2,
+ * as scikit-image 0.22 and later read that call (multichannel is ignored, channel_axis=0 holds; earlier releases fail on a [3,H,W]
+ * array).  Per channel, over the (H-6) x (W-6) positions whose 7x7 window lies wholly inside the image: the uniform means ux, uy, uxx,
+ * uyy, uxy, the sample covariances v = (49/48)(uxx - ux^2) ..., C1 = (0.01 R)^2, C2 = (0.03 R)^2,
+ *     S = (2 ux uy + C1)(2 vxy + C2) / ((ux^2 + uy^2 + C1)(vx + vy + C2)),
+ * its mean per channel, and the mean of the three channels.  One pass gives both R.  row: DEVICE double[4], all four written on every
+ * call:
+ *     row[0] SKSSIM (R = 1)   row[1] SKSSIM2 (R = 2)   row[2] number of scored positions whose S(R = 1) is not finite (exact)   row[3] 0
+ * img, gt, pixel_stride and lut exactly as in ex4d_frame_metrics / _u8.  flags: EX4D_METRICS_CLAMP only (scores clamp(img, 0, 1): a
+ * NaN stays a NaN, +-inf become 1 / 0); any other bit is refused, as are H < 7 and W < 7 (scikit-image raises there).
+ * scratch: ex4d_frame_skssim_scratch_floats(H, W) floats (0 for a refused size).  No allocation, no copy, no synchronisation: the calls
+ * can be captured into a graph.  Equal image and ground truth score exactly 1. */
+#define EX4D_SKSSIM_WINDOW 7
+size_t ex4d_frame_skssim_scratch_floats(int32_t H, int32_t W);
+int ex4d_frame_skssim(int32_t H, int32_t W, const float *img, const float *gt, int32_t flags, double *row /* device [4] */,
+                      float *scratch, void *stream);
+int ex4d_frame_skssim_u8(int32_t H, int32_t W, const float *img, const uint8_t *gt, int32_t pixel_stride,
+                         const float *lut /* host [256] or NULL */, int32_t flags, double *row /* device [4] */, float *scratch,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif
