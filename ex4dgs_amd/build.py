@@ -27,6 +27,7 @@ SOURCES = {
     "ex4d_api.hip": [],
     "ex4d_attributes.hip": ["-ffp-contract=off"],
     "ex4d_loss.hip": [],
+    "ex4d_frames.hip": ["-ffp-contract=off"],       # PIL's resize (declared in ex4d_loss.h): the coefficient table's doubles must not fuse
     "ex4d_optim.hip": ["-ffp-contract=off"],
     "ex4d_knn.hip": ["-ffp-contract=off"],
     "ex4d_densify.hip": ["-ffp-contract=off"],      # density control: threshold decisions and copied values follow torch's float32 ops
@@ -91,6 +92,14 @@ def _no_shift_amount_in_last_vgpr(src, obj):
                            f"allocated at the top of the register file): {bad}; change the kernel's __launch_bounds__ / register pressure")
 
 
+def _no_packed_shift_clamps(src, obj):
+    bad = isa_check.packed_shift_clamps(obj)
+    if bad:
+        os.remove(obj)
+        raise RuntimeError(f"{src}: v_ashr_pk_* (its destination's upper 16 bits are used as zero and are not, on gfx950): {bad}; clamp the "
+                           f"accumulator before the shift")
+
+
 def _report_wait_state_violations(src, obj):
     """Missing software wait states around the inline assembly (isa_check.wait_state_violations): reported, not fatal -- the rules are
     restated from the compiler's hazard recognizer, and tests/test_cpu_oracle_and_host.py holds the objects to zero findings."""
@@ -132,6 +141,7 @@ def build(force=False, verbose=False, extra_flags=()):
                 raise subprocess.CalledProcessError(r.returncode, cmd)
             _no_vgpr_spills(src, remarks, o)
             _no_shift_amount_in_last_vgpr(src, o)
+            _no_packed_shift_clamps(src, o)
             _report_wait_state_violations(src, o)
     if force or _stale(LIB, objs):
         cmd = [hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", LIB] + objs

@@ -832,6 +832,13 @@ bool check_skssim_args(int H, int W, const void *img, const void *gt, int flags,
 
 }  // namespace
 
+// the text ex4d_loss_last_error returns, for ex4d_frames.hip (the same header, the same error channel)
+char *ex4d_loss_error_buffer(size_t *capacity)
+{
+    *capacity = sizeof(g_loss_err);
+    return g_loss_err;
+}
+
 extern "C" {
 
 const char *ex4d_loss_last_error(void) { return g_loss_err; }

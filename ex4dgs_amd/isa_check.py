@@ -151,6 +151,23 @@ def shift_amount_in_last_vgpr(obj, tmpdir=None):
             shutil.rmtree(d, ignore_errors=True)
 
 
+def packed_shift_clamps(obj, tmpdir=None):
+    """[(kernel, instruction)] for every v_ashr_pk_* of the object's gfx950 code.  The instruction (new on gfx950) shifts two accumulators,
+    saturates them and packs them into the LOW 16 bits of its destination; the compiler selects it for `clamp(a >> n, 0, 255) |
+    clamp(b >> n, 0, 255) << 8` and goes on as if the destination's upper 16 bits were zero, which they were not on the MI355X when the
+    vertical resize pass (ex4d_frames.hip) packed four such bytes into a dword: bytes 2 and 3 came out wrong.  No kernel of this library
+    needs the instruction; one that gets it is rewritten (clamp the accumulator, then shift)."""
+    d = tmpdir or tempfile.mkdtemp(prefix="ex4d_isa_")
+    try:
+        co = device_code(obj, d)
+        if co is None:
+            return []
+        return [(kernel, t) for kernel, run in disassembly(co) for t in run if t.startswith("v_ashr_pk_")]
+    finally:
+        if not tmpdir:
+            shutil.rmtree(d, ignore_errors=True)
+
+
 # ------------------------------------------------------------------------------------------------ wait states
 def _regs(tok):
     """Register names an operand token covers: 'v5' -> {'v5'}, 'v[4:7]' -> v4..v7, 's[4:5]', 'vcc', 'exec', '-v3', '|v3|', 'v3 op_sel...'."""

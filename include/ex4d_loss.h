@@ -76,6 +76,45 @@ int ex4d_frame_metrics_u8(int32_t H, int32_t W, const float *img, const uint8_t 
                           const float *lut /* host [256] or NULL */, const float *window /* host [11] */, int32_t flags,
                           uint8_t *out_u8 /* [H,W,3] or NULL */, double *row /* device [8] */, float *scratch, void *stream);
 
+/* RESIZING a decoded frame to the training resolution, bit for bit as PIL's 8-bit Image.resize does (the reference's
+ * PILtoTorch(image, resolution), utils/general_utils.py:23-24: resample=2, bilinear with its support scaled by the reduction): two
+ * fixed-point passes, horizontal then vertical, with the intermediate image rounded to bytes between them.  Per axis of input size
+ * `in` and output size `out`, filter f of support s, in double precision with no contracted multiply-add:
+ *     scale = in / out;  fs = max(scale, 1);  sup = s * fs;  ksize = (int)ceil(sup) * 2 + 1;  ss = 1 / fs
+ *     per output element xx:  center = (xx + 0.5) * scale
+ *         xmin = max((int)(center - sup + 0.5), 0);  xmax = min((int)(center + sup + 0.5), in);  n = xmax - xmin
+ *         w[x] = f((x + xmin - center + 0.5) * ss), x < n;  ww = w[0] + w[1] + ...;  w[x] /= ww where ww != 0
+ *         k[x] = (int)(w[x] * 2^22 + 0.5) for w[x] >= 0, else (int)(w[x] * 2^22 - 0.5)
+ * and a pass computes acc = 2^21 + sum_{x<n} src[xmin + x] * k[x] in int32 and writes clamp(acc >> 22, 0, 255).  A pass whose input
+ * size equals its output size is skipped; if both are, the frame is copied.
+ * filter: PIL's resample numbers.  BILINEAR f(x) = 1 - |x| on |x| < 1, s = 1;  BOX f = 1 on (-0.5, 0.5], s = 0.5;  BICUBIC a = -0.5,
+ * s = 2.  (Lanczos and Hamming go through libm's sin / cos: not offered.)
+ * ex4d_resize_u8_table is HOST code: it fills ex4d_resize_u8_table_words(in, out, filter) words of one axis -- ksize, then per output
+ * element xmin, n and ksize coefficients (the unused ones zero); the caller uploads them once per (in, out, filter).  The words count
+ * is 0 for a refused size or filter.
+ * ex4d_resize_u8: src DEVICE uint8 [H_in,W_in,3], dst DEVICE uint8 [H_out,W_out,3], tightly packed, at any byte alignment; table_x
+ * (W_in -> W_out) and table_y (H_in -> H_out) DEVICE tables, either may be NULL where its pass is skipped; scratch:
+ * ex4d_resize_u8_scratch_bytes bytes (the [H_in,W_out,3] intermediate; 0 where a pass is skipped), written before it is read.  No
+ * byte outside src is read, none outside dst and the scratch is written, every byte of dst is written.  Sizes 1 .. EX4D_FRAME_MAX_SIZE
+ * per axis in any ratio.  pixel_stride must be 3: PIL resizes four-byte (RGBA) pixels on premultiplied colour, which gives other
+ * colour bytes than the RGB resize, and that is not reproduced here.  No allocation, no host-device copy, no synchronisation: the
+ * call can be captured into a graph.
+ * Tiling: the horizontal pass gives a workgroup EX4D_RESIZE_H_ROWS rows of EX4D_RESIZE_H_PIXELS output pixels, one lane per pixel; the
+ * vertical pass gives it EX4D_RESIZE_V_ROWS output rows of EX4D_RESIZE_V_BYTES flat bytes (3 W_out per row), four bytes per lane. */
+#define EX4D_FILTER_BILINEAR 2
+#define EX4D_FILTER_BICUBIC 3
+#define EX4D_FILTER_BOX 4
+#define EX4D_FRAME_MAX_SIZE 16384
+#define EX4D_RESIZE_H_PIXELS 64
+#define EX4D_RESIZE_H_ROWS 4
+#define EX4D_RESIZE_V_BYTES 256
+#define EX4D_RESIZE_V_ROWS 4
+size_t ex4d_resize_u8_table_words(int32_t in, int32_t out, int32_t filter);
+int ex4d_resize_u8_table(int32_t in, int32_t out, int32_t filter, int32_t *host_words);
+size_t ex4d_resize_u8_scratch_bytes(int32_t H_in, int32_t W_in, int32_t H_out, int32_t W_out);
+int ex4d_resize_u8(int32_t H_in, int32_t W_in, int32_t H_out, int32_t W_out, int32_t pixel_stride, const uint8_t *src, uint8_t *dst,
+                   const int32_t *table_x /* device */, const int32_t *table_y /* device */, uint8_t *scratch, void *stream);
+
 /* scikit-image's SSIM of a rendered view: the SKSSIM and SKSSIM2 entries of render.py:78-79,
  *     sk_ssim(render, gt, data_range=R, multichannel=True, channel_axis=0)   with R = 1 and R = 2,
  * as scikit-image 0.22 and later read that call (multichannel is ignored, channel_axis=0 holds; earlier releases fail on a [3,H,W]
