@@ -308,9 +308,24 @@ def test_sh_storage_smaller_than_16(hip_lib_both):
     _fwd_bwd("cfg1", sh_degree=1, mutate=mutate)
 
 
-def test_technicolor_resolution_14_bit_tiles(hip_lib):
-    """2048x1088 = 128x68 = 8704 tiles: the tile sort needs 14 key bits (two radix passes, 8 + 6)."""
-    o, g, *_ = _fwd_bwd("cfg5", P=3000, t=0)
+def _with_tile_sort_rows(rows, run):
+    """run() with the option "tile_sort_rows" set to `rows`; what it was comes back whatever run() does"""
+    from ex4dgs_amd import _C
+    saved = _C.get_option("tile_sort_rows")
+    try:
+        _C.set_option("tile_sort_rows", rows)
+        return run()
+    finally:
+        _C.set_option("tile_sort_rows", saved)
+
+
+@pytest.mark.parametrize("tile_sort_rows", [1, 0])
+def test_technicolor_resolution_14_bit_tiles(hip_lib, tile_sort_rows):
+    """2048x1088 = 128x68 = 8704 tiles, 14 tile bits.  tile_sort_rows = 1 (the default): the row-segment sort -- 68 tile rows
+    (rows_seg_scatter_kernel<128, .>), pass B with 7-bit columns.  tile_sort_rows = 0: the MSD pair sort with a 7-bit high and a 7-bit
+    low digit (TS_SCATTER_A(7), TS_SCATTER_B(7)), which this test was written for and which the default stopped reaching when the
+    row-segment sort became it."""
+    o, g, *_ = _with_tile_sort_rows(tile_sort_rows, lambda: _fwd_bwd("cfg5", P=3000, t=0))
     assert o["W"] == 2048 and o["H"] == 1088 and o["ranges"].shape[0] == 8704
 
 
@@ -777,13 +792,17 @@ def test_more_than_65535_tiles(hip_lib):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("tile_sort_rows", [1, 0])
 @pytest.mark.parametrize("side,bits", [(2300, 15), (2900, 16)])
-def test_tile_sort_with_15_and_16_tile_bits(hip_lib, side, bits):
-    """144x144 = 20 736 and 182x182 = 33 124 tiles: the MSD tile sort with 8-bit low digits and 7- / 8-bit high digits (the compile-time
-    digit widths the 1352x1014 and 2048x1088 configurations do not reach)."""
+def test_tile_sort_with_15_and_16_tile_bits(hip_lib, side, bits, tile_sort_rows):
+    """144x144 = 20 736 and 182x182 = 33 124 tiles.  tile_sort_rows = 0: the MSD pair sort with 8-bit low digits and 7- / 8-bit high
+    digits (TS_SCATTER_A(7) / TS_SCATTER_A(8), TS_SCATTER_B(8), ts_locate_block over 128 / 256 buckets: the compile-time digit widths the
+    1352x1014 and 2048x1088 configurations do not reach) -- what this test was written for.  tile_sort_rows = 1 (the default, which
+    silently took these scenes over when the row-segment sort became it): rows_seg_scatter_kernel<256, .> over 144 / 182 tile rows and
+    pass B with 8-bit columns."""
     from ex4dgs_amd.scene import SceneConfig
     cfg = SceneConfig(f"{side}x{side}", 1200, side, side, side * 0.55, seed=37 + bits, sigma_px_med=22.0)
-    o, g, *_ = _fwd_bwd(cfg)
+    o, g, *_ = _with_tile_sort_rows(tile_sort_rows, lambda: _fwd_bwd(cfg))
     T = o["ranges"].shape[0]
     assert T == ((side + 15) // 16) ** 2 and (1 << (bits - 1)) < T <= (1 << bits) and o["num_rendered"] > 10000
 
