@@ -155,9 +155,21 @@ def _p(t):
     return None if t is None else t.data_ptr()
 
 
-def _split_parts(shs, n_static):
-    """[P,16,3] -> (dc static, rest static, dc dynamic, rest dynamic), each its own contiguous tensor (an empty part keeps 0 rows)."""
-    return [shs[:n_static, :1].contiguous(), shs[:n_static, 1:].contiguous(), shs[n_static:, :1].contiguous(), shs[n_static:, 1:].contiguous()]
+def _split_parts(shs, n_static, offset=0):
+    """[P,16,3] -> (dc static, rest static, dc dynamic, rest dynamic), each its own contiguous tensor (an empty part keeps 0 rows).
+    offset: each part starts this many elements into its own allocation (4 * offset bytes behind torch's 256-byte alignment)."""
+    parts = [shs[:n_static, :1].contiguous(), shs[:n_static, 1:].contiguous(), shs[n_static:, :1].contiguous(), shs[n_static:, 1:].contiguous()]
+    if offset:
+        parts = [_offset_view(torch.empty(p.numel() + offset, dtype=p.dtype, device=p.device), p.shape, offset).copy_(p) for p in parts]
+    return parts
+
+
+def _offset_view(flat, shape, offset):
+    """The tensor of `shape` that starts `offset` elements into the 1-d tensor `flat`."""
+    n = 1
+    for d in shape:
+        n *= d
+    return flat[offset: offset + n].view(*shape)
 
 
 def _split_struct(parts, n_static):
@@ -167,9 +179,10 @@ def _split_struct(parts, n_static):
 
 
 def forward(ins, settings, bufs, fill="zero", state_fill=None, subpixel_offset=None, prepare_backward=False, instance_capacity=0,
-            assume_no_flow=False, n_static=None, device="cuda"):
+            assume_no_flow=False, n_static=None, split_offset=0, device="cuda"):
     """ex4d_forward / ex4d_forward_split_sh (n_static given: the SH tensor is passed as its four parts) with every buffer in `bufs`.
     fill: outputs (and the status words of an asynchronous forward); state_fill: the three state buffers (default: the same).
+    split_offset: the four SH parts start this many floats into their allocations (_split_parts).
     Returns helpers.gpu_forward_raw's dictionary + rc / requested bytes / the Buffers."""
     from ex4dgs_amd import _C
     from tests import helpers as h
@@ -214,7 +227,7 @@ def forward(ins, settings, bufs, fill="zero", state_fill=None, subpixel_offset=N
         tail = (cbs[0], None, cbs[1], None, cbs[2], None, out["color"].data_ptr(), out["radii"].data_ptr(), out["depth"].data_ptr(),
                 out["acc"].data_ptr(), out["flow"].data_ptr(), out["idx"].data_ptr(), stream, count_ref)
         if split:
-            keep = _split_parts(t["shs"], n_static)
+            keep = _split_parts(t["shs"], n_static, split_offset)
             st = _split_struct(keep, n_static)
             rc = lib.ex4d_forward_split_sh(C.byref(prm), _p(cam["bg"]), _p(t["means3D"]), _p(t["dir3D"]), C.byref(st), _p(t["opacities"]),
                                            _p(t["scales"]), _p(t["rotations"]), _p(t["cov3D_precomp"]), _p(cam["viewmatrix"]), _p(cam["projmatrix"]),
@@ -244,10 +257,12 @@ def forward(ins, settings, bufs, fill="zero", state_fill=None, subpixel_offset=N
     return res
 
 
-def backward(fwd, grads, bufs=None, fill="zero", prepared=False, null_outputs=(), null_grads=(), device="cuda"):
+def backward(fwd, grads, bufs=None, fill="zero", prepared=False, null_outputs=(), null_grads=(), split_grad_offset=0, device="cuda"):
     """ex4d_backward / ex4d_backward_split_sh on the state a forward of this driver left (same inputs, same Buffers unless `bufs` is
     given).  fill: the gradient outputs and the scratch.  null_outputs: of ("dL_dcolors", "dL_dcov3D") passed as NULL;
     null_grads: indices 0..3 of the upstream gradients (colour, depth, flow, acc) passed as NULL.
+    split_grad_offset: the four gradient parts of the split layout start this many floats into their (guarded, prefilled) payloads;
+    the floats in front of them come back under "split_grad_lead".
     Returns helpers.gpu_backward_raw's dictionary (split SH: dL_dsh is the four parts concatenated back to [P,16,3], the parts
     themselves under SPLIT_GRAD_NAMES) + rc."""
     from ex4dgs_amd import _C
@@ -274,7 +289,8 @@ def backward(fwd, grads, bufs=None, fill="zero", prepared=False, null_outputs=()
         n = 4
         for d in shape:
             n *= d
-        out[name] = bufs.prepare(name, n, fill).view(torch.float32, *shape)
+        lead = split_grad_offset if name in SPLIT_GRAD_NAMES else 0
+        out[name] = _offset_view(bufs.prepare(name, n + 4 * lead, fill).payload.view(torch.float32), shape, lead)
     scratch = bufs.prepare("scratch", int(lib.ex4d_backward_scratch_bytes(P)), fill)
     optr = lambda n: out[n].data_ptr() if (n in out and out[n].numel()) else None
     state = [bufs.get(n).ptr for n in STATE_BUFFERS]
@@ -299,6 +315,7 @@ def backward(fwd, grads, bufs=None, fill="zero", prepared=False, null_outputs=()
     if rc != 0:
         return res
     if split:
+        res["split_grad_lead"] = {n: bufs.get(n).payload.view(torch.float32)[:split_grad_offset] for n in SPLIT_GRAD_NAMES}
         res["dL_dsh"] = torch.cat([torch.cat([out["dL_dsh_dc_static"], out["dL_dsh_rest_static"]], 1),
                                    torch.cat([out["dL_dsh_dc_dynamic"], out["dL_dsh_rest_dynamic"]], 1)], 0)
     e = torch.empty(0, dtype=torch.float32, device=dev)
