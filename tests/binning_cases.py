@@ -141,21 +141,22 @@ CASE_NAMES = tuple(c.name for c in cases())
 SHORT_CASES = (("bucket4096", "rows"), ("bucket4096", "msd pair"), ("radix8", "radix pair"))
 
 
-@functools.lru_cache(maxsize=4)
-def scene(name):
-    """(inputs, settings) of a case: helpers.scene_inputs on a literal SceneConfig, then means3D / scales / opacities / rotations overwritten"""
-    c = case(name)
-    P = len(c.specs)
-    focal = 16.0 * max(c.W, c.H)
-    cfg = SceneConfig(f"binning case {name}", P, c.W, c.H, focal, seed=900 + CASE_NAMES.index(name), min_depth=MIN_DEPTH, max_depth=MAX_DEPTH)
+def build_scene(label, W, H, specs, z, ids, min_depth, max_depth, seed):
+    """(inputs, settings) of designed Gaussians: helpers.scene_inputs on a literal SceneConfig with these two planes, then means3D /
+    scales / opacities / rotations overwritten.  specs[i] = (pixel centre x, pixel centre y, radius, visible) of the i-th designed
+    Gaussian, z[i] its depth (a float32 value; the view is the identity, so it is p_view.z exactly), ids[i] its id."""
+    P = len(specs)
+    focal = 16.0 * max(W, H)
+    cfg = SceneConfig(label, P, W, H, focal, seed=seed, min_depth=min_depth, max_depth=max_depth)
     ins, st = h.scene_inputs(cfg, P=P)
-    ids = np.random.default_rng(7000 + CASE_NAMES.index(name)).permutation(P)          # the id of the i-th designed Gaussian
-    px, py, r, vis = (np.array([s[k] for s in c.specs], np.float64) for k in range(4))
-    z = np.where(vis > 0, 5.0 + 0.01 * (np.arange(P) // 2), 1.0).astype(np.float32).astype(np.float64)
+    px, py, r, vis = (np.array([s[k] for s in specs], np.float64) for k in range(4))
+    z = np.asarray(z, np.float32).astype(np.float64)
     # radius = ceil(3 sqrt(lambda)), lambda = (focal s / z)^2 + kernel_size + sqrt(0.1): aim at r - 0.5 (the smallest radius is 2)
     var = np.maximum(((r - 0.5) / 3.0) ** 2 - (0.1 + 0.1 ** 0.5), 0.01)
-    m = np.stack([(px + 0.5 - c.W / 2.0) * z / focal, (py + 0.5 - c.H / 2.0) * z / focal, z], -1)
-    s = np.repeat((z / focal * np.sqrt(var))[:, None], 3, 1)
+    m = np.stack([(px + 0.5 - W / 2.0) * z / focal, (py + 0.5 - H / 2.0) * z / focal, z], -1)
+    # (|z|: the same value for the depths in front of the camera; tests/depth_sort_cases.py has rows with a depth below zero under a
+    # negative near plane, whose scales must stay positive)
+    s = np.repeat((np.abs(z) / focal * np.sqrt(var))[:, None], 3, 1)
     op = np.where(r > 100, 1.0, 0.5)[:, None]          # the large ones opaque: the compositing behind them ends early
     for k, v in (("means3D", m), ("scales", s), ("opacities", op)):
         t = torch.zeros(ins[k].shape, dtype=torch.float32)
@@ -164,6 +165,17 @@ def scene(name):
     # (the generator's quaternions are not unit: a rotation matrix built from one scales the covariance; the identity keeps it isotropic)
     ins["rotations"] = torch.tensor([1.0, 0.0, 0.0, 0.0]).repeat(P, 1).contiguous()
     return ins, st
+
+
+@functools.lru_cache(maxsize=4)
+def scene(name):
+    """(inputs, settings) of a case: build_scene with the depths 5 + 0.01 (i // 2) (hidden: 1) between SceneConfig's default planes"""
+    c = case(name)
+    P = len(c.specs)
+    ids = np.random.default_rng(7000 + CASE_NAMES.index(name)).permutation(P)          # the id of the i-th designed Gaussian
+    vis = np.array([s[3] for s in c.specs], np.float64)
+    z = np.where(vis > 0, 5.0 + 0.01 * (np.arange(P) // 2), 1.0).astype(np.float32)
+    return build_scene(f"binning case {name}", c.W, c.H, c.specs, z, ids, MIN_DEPTH, MAX_DEPTH, 900 + CASE_NAMES.index(name))
 
 
 # ------------------------------------------------------------------------------------------------ the restatement
@@ -191,10 +203,10 @@ def rects_of(radii, means2D, W, H):
 
 
 def host_depth_order(radii, depths):
-    """tests/test_gpu_round5.py: _host_depth_order, in numpy: stable ascending sort of the visible depths' bit patterns, ties in
-    ascending id, invisible Gaussians behind in id order"""
+    """tests/test_gpu_round5.py: _host_depth_order, in numpy: stable ascending sort of the visible depths' bit patterns as unsigned
+    32-bit words, ties in ascending id, invisible Gaussians behind in id order"""
     radii = _np(radii)
-    bits = np.ascontiguousarray(_np(depths), np.float32).view(np.int32).astype(np.int64)
+    bits = np.ascontiguousarray(_np(depths), np.float32).view(np.uint32).astype(np.int64)
     return np.argsort(np.where(radii > 0, bits, 1 << 40), kind="stable").astype(np.int64)
 
 

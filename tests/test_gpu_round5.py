@@ -32,10 +32,10 @@ def _frame(ins, st, **options):
 
 
 def _host_depth_order(fr):
-    """Stable ascending sort of the visible Gaussians' depth bit patterns (CR/rasterizer_impl.cu:106: the low key word), ties in
-    ascending id, invisible Gaussians behind them in id order."""
+    """Stable ascending sort of the visible Gaussians' depth bit patterns as unsigned 32-bit words (CR/rasterizer_impl.cu:106: the low
+    key word), ties in ascending id, invisible Gaussians behind them in id order."""
     vis = fr["radii"] > 0
-    bits = fr["depths"].contiguous().view(torch.int32).to(torch.int64)
+    bits = fr["depths"].contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
     key = torch.where(vis, bits, torch.full_like(bits, 1 << 40))
     return torch.sort(key, stable=True).indices.to(torch.int32)
 
