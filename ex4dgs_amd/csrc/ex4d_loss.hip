@@ -17,7 +17,11 @@
 // the backward needs; backward convolves those three maps with the same (symmetric) window and combines them with the pixel values:
 //     d(sum ssim)/dx_p = conv(A)_p + 2 x_p conv(B)_p + y_p conv(C)_p,   A = dS/dmu1, B = dS/dE[x^2], C = dS/dE[xy].
 //
-// GROUND TRUTH AS DECODED (ex4d_l1_ssim_*_u8): both kernels are templates over the ground truth's element type -- float32 [C,H,W] planes,
+// THE SCHEME IS WRITTEN ONCE (Stage, Tile, walk, block_sum below) and the four kernels -- the loss's forward and backward, and the two
+// that score a rendered view, frame_metrics_kernel and frame_skssim_kernel -- pass in what differs: the maps they stage (ImagePair,
+// DerivMaps), their row pass and their column pass.
+//
+// GROUND TRUTH AS DECODED (ex4d_l1_ssim_*_u8): the kernels are templates over the ground truth's element type -- float32 [C,H,W] planes,
 // or uint8 [H,W,S] pixels (S = 3 or 4, as an image decoder leaves them) looked up in a 256-entry float table, which the uint8
 // instantiations take as one more kernel argument.  Everything behind the load is the same code, so the two agree bit for bit on equal
 // values; the float instantiations keep the signature and the loads they had.  THE TABLE travels in the kernel
@@ -40,14 +44,6 @@ namespace {
 #define RPI 4                       // image rows per iteration (256 threads = RPI rows x SW columns)
 #define RING 16                     // rows of row-pass results kept in LDS (>= 11 + RPI - 1, power of two)
 #define CG 3                        // channels convolved together (the reference's images are RGB; more channels run in groups)
-
-// static LDS of the two kernels: the input double buffer + the ring of row-pass results.  Both exceed the 64 KB a workgroup may take on
-// older parts and are sized for gfx950's 160 KB per CU (two workgroups per CU): this file builds for gfx950-class LDS only
-static_assert(sizeof(float) * (2 * 2 * CG * RPI * (SIN + 2) + CG * 5 * RING * SW + 8) <= 80 * 1024, "l1_ssim_fwd_kernel: two workgroups per CU need <= 80 KB of LDS each");
-static_assert(sizeof(float) * (2 * 3 * CG * RPI * (SIN + 2) + CG * 3 * RING * SW) <= 80 * 1024, "l1_ssim_bwd_kernel: two workgroups per CU need <= 80 KB of LDS each");
-
-static_assert(sizeof(float) * (2 * 2 * CG * RPI * (SIN + 2) + CG * 5 * RING * SW + 8 + 256) <= 80 * 1024, "l1_ssim_fwd_kernel<uint8_t>: the table joins the same budget");
-static_assert(sizeof(float) * (2 * 3 * CG * RPI * (SIN + 2) + CG * 3 * RING * SW + 256) <= 80 * 1024, "l1_ssim_bwd_kernel<uint8_t>: the table joins the same budget");
 
 struct Window { float w[EX4D_SSIM_WINDOW]; };
 
@@ -78,177 +74,308 @@ __device__ __forceinline__ int work_item_of_block(int nwork)
     return (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
 }
 
-// (frame_metrics_kernel below repeats this kernel's fetch / commit / ring / barrier scheme: a fix to the window scheme belongs in both)
+// ---- the static LDS of a kernel: the double buffer of an iteration's rows, NMAP staged maps of CG channels with HALF halo columns per
+// side (+ 2 columns of padding), and the ring of NRING row-pass results per channel.  It exceeds the 64 KB a workgroup may take on
+// older parts and is sized for gfx950's 160 KB per CU (two workgroups per CU): this file builds for gfx950-class LDS only
+template <int NMAP, int NRING, int HALF>
+struct Stage {
+    static_assert(RING >= 2 * HALF + RPI && (RING & (RING - 1)) == 0, "the ring holds a window and an iteration");
+    static_assert(RPI * 2 * HALF <= 256, "one halo load per thread");
+    float in[2][NMAP][CG][RPI][SW + 2 * HALF + 2];      // [buffer][map][channel][row][column]
+    float ring[CG][NRING][RING][SW];                    // row-pass results of the last RING image rows
+};
+
+// a kernel's whole LDS: its Stage, the NSUMS x 4 floats of its block_sum and, in a _u8 instantiation, the workgroup's copy of the table
+template <typename St, int NSUMS, typename... Table>
+constexpr bool two_workgroups_per_cu = sizeof(St) + NSUMS * 4 * sizeof(float) + (sizeof(Table::v) + ... + 0) <= 80 * 1024;
+
+// ---- a workgroup's tile and a thread's roles in it.  Work item wi is strip wi % nsx, segment wi / nsx of an Ho x Wo output domain;
+// output (oy, ox) reads image rows oy - HALF .. oy + HALF and the same columns where the image is PADDED with zeros (the 11-tap
+// kernels), rows oy .. oy + 2 HALF and the same columns, all inside the image, where it is not (the output domain is the image less
+// HALF pixels per side).  An iteration's rows: every thread takes column (tid & 63) of row (tid >> 6) in every plane (map x channel),
+// threads 0 .. RPI * 2 HALF - 1 also one of the RPI x 2 HALF halo columns 64 .. -- two loads per plane with ONE pixel offset each (a
+// flat element index decoded per load kept ~100 registers of hoisted address arithmetic alive)
+template <int HALF, bool PADDED>
+struct Tile {
+    int col, rsub, hrow, hcol;
+    bool has_halo;
+    int x0, y0;                     // first output column / row
+    int xr, yr;                     // first image column / row read
+    int rows_out, n_in, n_it;       // output rows, image rows read (rows_out + 2 HALF), iterations
+    int px, Wo;                     // this thread's output column; the output domain's width
+    __device__ __forceinline__ Tile(int wi, int nsx, int Ho, int Wo_) : Wo(Wo_)
+    {
+        col = threadIdx.x & (SW - 1); rsub = threadIdx.x >> 6;
+        hrow = (int)threadIdx.x / (2 * HALF); hcol = SW + (int)threadIdx.x % (2 * HALF);
+        has_halo = threadIdx.x < RPI * 2 * HALF;
+        x0 = (wi % nsx) * SW; y0 = (wi / nsx) * SEG;
+        xr = x0 - (PADDED ? HALF : 0); yr = y0 - (PADDED ? HALF : 0);
+        rows_out = (Ho - y0) < SEG ? (Ho - y0) : SEG;
+        n_in = rows_out + 2 * HALF;
+        n_it = (n_in + RPI - 1) / RPI;
+        px = x0 + col;
+    }
+    // row ro of the segment (of this thread's column) is an output pixel
+    __device__ __forceinline__ bool is_output(int ro) const { return ro >= 0 && ro < rows_out && px < Wo; }
+};
+
+// ---- what a walk stages.  load(map, channel, in_image, pixel offset) is the value kept in flight, commit(map, main, halo) makes of a
+// thread's two values of a plane what goes to LDS (both under ONE test of a uniform condition: the compiler then keeps it a branch).
+// The image and the ground truth of channels c0 .. c0 + nc - 1: float planes, or (the ground truth of a _u8 instantiation) the byte,
+// which stays in flight and is looked up at commit.  Beyond the image a plane is 0 (conv2d padding=5; frame_skssim_kernel's feed
+// masked outputs only).  clamp01: the image is clamped to [0,1] as torch.clamp does -- a NaN stays a NaN, the padding's 0 stays 0
+template <typename T>
+struct ImagePair {
+    static constexpr bool kBytes = sizeof(T) == 1;
+    const float *__restrict__ img;
+    const T *__restrict__ gt;
+    size_t HW;
+    PixelLds px8;
+    int c0, nc;
+    bool clamp01;
+    __device__ __forceinline__ float load(int map, int ch, bool ok, size_t o) const
+    {
+        ok = ok && ch < nc;
+        if constexpr (kBytes) {
+            if (map) return byte_bits(ok, gt, o * px8.S + (c0 + ch));
+        }
+        const float *src = (map ? (const float *)gt : img) + (size_t)(c0 + ch) * HW;
+        return ok ? src[o] : 0.f;
+    }
+    __device__ __forceinline__ void commit(int map, float &vm, float &vh) const
+    {
+        if (map) {
+            if constexpr (kBytes) { vm = byte_value(vm, px8.v); vh = byte_value(vh, px8.v); }
+        } else if (clamp01) {
+            const float a = vm, b = vh;                  // (arms that are values stay selects; read through the references they
+            vm = a < 0.f ? 0.f : (a > 1.f ? 1.f : a);    // become divergent branches: 1 us of frame_skssim's 43)
+            vh = b < 0.f ? 0.f : (b > 1.f ? 1.f : b);
+        }
+    }
+};
+
+// the forward's three derivative maps [3][C][H][W], channels c0 .. c0 + nc - 1
+struct DerivMaps {
+    const float *__restrict__ dmaps;
+    size_t HW;
+    int C, c0, nc;
+    __device__ __forceinline__ float load(int map, int ch, bool ok, size_t o) const
+    {
+        const float *src = dmaps + ((size_t)map * C + c0 + ch) * HW;
+        return (ok && ch < nc) ? src[o] : 0.f;
+    }
+    __device__ __forceinline__ void commit(int, float &, float &) const {}
+};
+
+// ---- the walk down a segment.  row_pass(buf, rin) convolves image row rin (relative to the first row read) of buffer buf into the
+// ring, col_pass(ro) takes output row ro, whose window (ring rows ro .. ro + 2 HALF) is complete.  The leading barrier: the previous
+// channel group is done with both buffers and the ring, and a _u8 instantiation's table is published
+template <int NMAP, int NRING, int HALF, bool PADDED, typename Maps, typename RowPass, typename ColPass>
+__device__ __forceinline__ void walk(const Tile<HALF, PADDED> &t, int H, int W, Stage<NMAP, NRING, HALF> &s, const Maps &maps,
+                                     RowPass row_pass, ColPass col_pass)
+{
+    float rm[NMAP * CG], rh[NMAP * CG];
+    auto fetch = [&](int it) {
+        const int ym = t.yr + it * RPI + t.rsub, xm = t.xr + t.col;
+        const int yh = t.yr + it * RPI + t.hrow, xh = t.xr + t.hcol;
+        const bool okm = xm >= 0 && xm < W && ym >= 0 && ym < H, okh = t.has_halo && xh >= 0 && xh < W && yh >= 0 && yh < H;
+        const size_t om = (size_t)ym * W + xm, oh = (size_t)yh * W + xh;
+#pragma unroll
+        for (int pl = 0; pl < NMAP * CG; pl++) {
+            rm[pl] = maps.load(pl / CG, pl % CG, okm, om);
+            rh[pl] = maps.load(pl / CG, pl % CG, okh, oh);
+        }
+    };
+    auto commit = [&](int buf) {
+#pragma unroll
+        for (int pl = 0; pl < NMAP * CG; pl++) {
+            float vm = rm[pl], vh = rh[pl];
+            maps.commit(pl / CG, vm, vh);
+            s.in[buf][pl / CG][pl % CG][t.rsub][t.col] = vm;
+            if (t.has_halo) s.in[buf][pl / CG][pl % CG][t.hrow][t.hcol] = vh;
+        }
+    };
+    __syncthreads();
+    fetch(0);
+    commit(0);
+    __syncthreads();
+    for (int it = 0; it < t.n_it; it++) {
+        const int buf = it & 1;
+        if (it + 1 < t.n_it) fetch(it + 1);             // in flight while this iteration's rows are convolved
+        const int rin = it * RPI + t.rsub;
+        if (rin < t.n_in) row_pass(buf, rin);
+        __syncthreads();
+        const int ro = rin - 2 * HALF;
+        if (t.is_output(ro)) col_pass(ro);
+        if (it + 1 < t.n_it) commit(buf ^ 1);
+        __syncthreads();
+    }
+}
+
+// ---- the 11-tap pieces.  The row pass of one channel: the five moment maps x, y, x^2, y^2, xy of the windows that start at sx, sy
+__device__ __forceinline__ void moments_row(const Window &win, const float *sx, const float *sy, float (&m)[5])
+{
+    float m1 = 0.f, m2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
+#pragma unroll
+    for (int k = 0; k < EX4D_SSIM_WINDOW; k++) {
+        const float a = sx[k], b = sy[k], wk = win.w[k];
+        m1 += wk * a; m2 += wk * b; e11 += wk * (a * a); e22 += wk * (b * b); e12 += wk * (a * b);
+    }
+    m[0] = m1; m[1] = m2; m[2] = e11; m[3] = e22; m[4] = e12;
+}
+
+// the column pass of one channel's N ring maps at output row ro
+template <int N>
+__device__ __forceinline__ void taps_col(const Window &win, const float (&ring)[N][RING][SW], int ro, int col, float (&m)[N])
+{
+#pragma unroll
+    for (int q = 0; q < N; q++) m[q] = 0.f;
+#pragma unroll
+    for (int k = 0; k < EX4D_SSIM_WINDOW; k++) {
+        const float wk = win.w[k];
+        const int slot = (ro + k) & (RING - 1);
+#pragma unroll
+        for (int q = 0; q < N; q++) m[q] += wk * ring[q][slot][col];
+    }
+}
+
+template <int N>
+__device__ __forceinline__ void ring_put(float (&ring)[N][RING][SW], int rin, int col, const float (&m)[N])
+{
+#pragma unroll
+    for (int q = 0; q < N; q++) ring[q][rin & (RING - 1)][col] = m[q];
+}
+
+// utils/loss_utils.py:61-74 from the window's five moments (mu1, mu2, E[x^2], E[y^2], E[xy])
+struct Ssim { float a1, a2, b1, b2, inv, S; };
+__device__ __forceinline__ Ssim ssim_of(const float (&m)[5])
+{
+    const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
+    const float mu1 = m[0], mu2 = m[1], e11 = m[2], e22 = m[3], e12 = m[4];
+    const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
+    const float s1 = e11 - mu1_sq, s2 = e22 - mu2_sq, s12 = e12 - mu12;
+    const float a1 = 2.f * mu12 + C1, a2 = 2.f * s12 + C2, b1 = mu1_sq + mu2_sq + C1, b2 = s1 + s2 + C2;
+    const float inv = 1.f / (b1 * b2);
+    return Ssim{ a1, a2, b1, b2, inv, (a1 * a2) * inv };
+}
+
+// ---- N sums over the workgroup's 256 threads: wave shuffle, then LDS; every thread returns with the four waves' totals added in a
+// fixed order (no single-address atomics: they serialise ~12 ns each)
+template <typename V, int N>
+__device__ __forceinline__ void block_sum(V (&v)[N])
+{
+    __shared__ V s[N][4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int q = 0; q < N; q++) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v[q] += __shfl_xor(v[q], o, 64);
+        if (lane == 0) s[q][wave] = v[q];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < N; q++) v[q] = s[q][0] + s[q][1] + s[q][2] + s[q][3];
+}
+
+// a workgroup's N float partial sums -> partials[N * workgroup ..]
+template <int N>
+__device__ __forceinline__ void put_partials(float (&v)[N], float *__restrict__ partials)
+{
+    block_sum(v);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int q = 0; q < N; q++) partials[N * blockIdx.x + q] = v[q];
+    }
+}
+
+// the one workgroup of a finish kernel: the N columns of the workgroups' partials, added in double
+template <int N>
+__device__ __forceinline__ void sum_partials(int nblocks, const float *__restrict__ partials, double (&sum)[N])
+{
+#pragma unroll
+    for (int q = 0; q < N; q++) sum[q] = 0.0;
+    for (int i = threadIdx.x; i < nblocks; i += 256) {
+#pragma unroll
+        for (int q = 0; q < N; q++) sum[q] += (double)partials[N * i + q];
+    }
+    block_sum(sum);
+}
+
 template <typename T, typename... Table>
 __global__ __launch_bounds__(256) void l1_ssim_fwd_kernel(int C, int H, int W, const float *__restrict__ img,
     const T *__restrict__ gt, Window win, float *__restrict__ l1_errors, float *__restrict__ ssim_errors,
     float *__restrict__ dmaps, float *__restrict__ partials, int nsx, int nsy, Table... table)
 {
-    constexpr bool kBytes = sizeof...(Table) != 0;
-    __shared__ float s_in[2][2][CG][RPI][SIN + 2];      // [buffer][x | y][channel][row][column]
-    __shared__ float s_ring[CG][5][RING][SW];           // row-pass results of the last RING image rows
-    __shared__ float s_red[2][4];
-    const PixelLds px8 = table_to_lds(table...);        // (published by the barrier in front of the first fetch)
+    using St = Stage<2, 5, LH>;                          // maps x | y; five moment maps
+    static_assert(two_workgroups_per_cu<St, 2, Table...>, "l1_ssim_fwd_kernel: two workgroups per CU need <= 80 KB of LDS each");
+    __shared__ St s;
+    const PixelLds px8 = table_to_lds(table...);
     const int nwork = nsx * nsy;
     const int wi = work_item_of_block(nwork);
-    const int col = threadIdx.x & (SW - 1), rsub = threadIdx.x >> 6;
     const size_t HW = (size_t)H * W;
-    const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
-    float l1_total = 0.f, ssim_total = 0.f;
+    float sums[2] = { 0.f, 0.f };                        // L1, SSIM
     if (wi < nwork) {
-        const int x0 = (wi % nsx) * SW, y0 = (wi / nsx) * SEG;
-        const int rows_out = (H - y0) < SEG ? (H - y0) : SEG;
-        const int n_in = rows_out + 2 * LH;              // image rows y0 - 5 .. y0 + rows_out + 4
-        const int n_it = (n_in + RPI - 1) / RPI;
-        const int px = x0 + col;
-        // an iteration's rows: every thread takes column (tid & 63) of row (tid >> 6) in every plane (image x channel), threads 0 .. 39
-        // also one of the 4 x 10 halo columns 64 .. 73 -- two loads per plane with ONE pixel offset each (a flat element index decoded
-        // per load kept ~100 registers of hoisted address arithmetic alive)
-        const int hrow = (int)threadIdx.x / (2 * LH), hcol = SW + (int)threadIdx.x % (2 * LH);
-        const bool has_halo = threadIdx.x < RPI * 2 * LH;
+        const Tile<LH, true> t(wi, nsx, H, W);
         for (int c0 = 0; c0 < C; c0 += CG) {
             const int nc = (C - c0) < CG ? (C - c0) : CG;
-            const bool first_group = c0 == 0, last_group = c0 + CG >= C;
-            float rm[2 * CG], rh[2 * CG];
-            auto fetch = [&](int it) {
-                const int ym = y0 - LH + it * RPI + rsub, xm = x0 - LH + col;
-                const int yh = y0 - LH + it * RPI + hrow, xh = x0 - LH + hcol;
-                const bool okm = xm >= 0 && xm < W && ym >= 0 && ym < H, okh = has_halo && xh >= 0 && xh < W && yh >= 0 && yh < H;
-                const size_t om = (size_t)ym * W + xm, oh = (size_t)yh * W + xh;
-#pragma unroll
-                for (int pl = 0; pl < 2 * CG; pl++) {
-                    const int ch = pl % CG;
-                    if constexpr (kBytes) {
-                        if (pl / CG) {                   // the BYTE stays in flight; commit looks it up
-                            rm[pl] = byte_bits(okm && ch < nc, gt, om * px8.S + (c0 + ch));
-                            rh[pl] = byte_bits(okh && ch < nc, gt, oh * px8.S + (c0 + ch));
-                        } else {
-                            const float *src = img + (size_t)(c0 + ch) * HW;
-                            rm[pl] = (okm && ch < nc) ? src[om] : 0.f;
-                            rh[pl] = (okh && ch < nc) ? src[oh] : 0.f;
-                        }
-                    } else {
-                        const float *src = ((pl / CG) ? gt : img) + (size_t)(c0 + ch) * HW;
-                        rm[pl] = (okm && ch < nc) ? src[om] : 0.f;       // zero padding (conv2d padding=5)
-                        rh[pl] = (okh && ch < nc) ? src[oh] : 0.f;
-                    }
-                }
+            // an error map over the channel groups: the first stores, the others add, the last divides by C
+            auto put_error = [&](float *map, int ro, float v) {
+                if (!map) return;
+                float *o = map + (size_t)(t.y0 + ro) * W + t.px;
+                if (c0 != 0) v = *o + v;
+                *o = (c0 + CG >= C) ? v / (float)C : v;
             };
-            auto commit = [&](int buf) {
-#pragma unroll
-                for (int pl = 0; pl < 2 * CG; pl++) {
-                    float vm = rm[pl], vh = rh[pl];
-                    if constexpr (kBytes) {
-                        if (pl / CG) { vm = byte_value(vm, px8.v); vh = byte_value(vh, px8.v); }
-                    }
-                    s_in[buf][pl / CG][pl % CG][rsub][col] = vm;
-                    if (has_halo) s_in[buf][pl / CG][pl % CG][hrow][hcol] = vh;
-                }
-            };
-            __syncthreads();                             // (the previous channel group is done with both buffers and the ring)
-            fetch(0);
-            commit(0);
-            __syncthreads();
-            for (int it = 0; it < n_it; it++) {
-                const int buf = it & 1;
-                if (it + 1 < n_it) fetch(it + 1);        // in flight while this iteration's rows are convolved
-                // ---- row pass of image row rin (relative to y0 - 5), five moment maps per channel -> ring; the L1 term of the pixels of
-                // this row (they are output pixels when the row lies inside the segment)
-                const int rin = it * RPI + rsub;
-                if (rin < n_in) {
+            walk(t, H, W, s, ImagePair<T>{ img, gt, HW, px8, c0, nc, false },
+                // ---- row pass: five moment maps per channel -> ring; the L1 term of the pixels of this row (they are output pixels when
+                // the row lies inside the segment)
+                [&](int buf, int rin) {
                     float l1 = 0.f;
 #pragma unroll 1
                     for (int ch = 0; ch < nc; ch++) {
-                        const float *sx = &s_in[buf][0][ch][rsub][col], *sy = &s_in[buf][1][ch][rsub][col];
-                        float m1 = 0.f, m2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
-#pragma unroll
-                        for (int k = 0; k < EX4D_SSIM_WINDOW; k++) {
-                            const float a = sx[k], b = sy[k], wk = win.w[k];
-                            m1 += wk * a; m2 += wk * b; e11 += wk * (a * a); e22 += wk * (b * b); e12 += wk * (a * b);
-                        }
-                        const int slot = rin & (RING - 1);
-                        s_ring[ch][0][slot][col] = m1; s_ring[ch][1][slot][col] = m2; s_ring[ch][2][slot][col] = e11;
-                        s_ring[ch][3][slot][col] = e22; s_ring[ch][4][slot][col] = e12;
+                        const float *sx = &s.in[buf][0][ch][t.rsub][t.col], *sy = &s.in[buf][1][ch][t.rsub][t.col];
+                        float m[5];
+                        moments_row(win, sx, sy, m);
+                        ring_put(s.ring[ch], rin, t.col, m);
                         l1 += fabsf(sx[LH] - sy[LH]);
                     }
                     const int ro = rin - LH;             // this image row as an output row of the segment
-                    if (ro >= 0 && ro < rows_out && px < W) {
-                        l1_total += l1;
-                        if (l1_errors) {
-                            float *o = l1_errors + (size_t)(y0 + ro) * W + px;
-                            const float v = first_group ? l1 : *o + l1;
-                            *o = last_group ? v / (float)C : v;
-                        }
+                    if (t.is_output(ro)) {
+                        sums[0] += l1;
+                        put_error(l1_errors, ro, l1);
                     }
-                }
-                __syncthreads();
-                // ---- column pass of output row ro: its window (image rows ro .. ro + 10 relative to y0 - 5) is complete
-                const int ro = it * RPI + rsub - 2 * LH;
-                if (ro >= 0 && ro < rows_out && px < W) {
+                },
+                // ---- column pass: the SSIM map's value and its three partial derivatives
+                [&](int ro) {
                     float ssim = 0.f;
 #pragma unroll 1
                     for (int ch = 0; ch < nc; ch++) {
-                        float mu1 = 0.f, mu2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
-#pragma unroll
-                        for (int k = 0; k < EX4D_SSIM_WINDOW; k++) {
-                            const float wk = win.w[k];
-                            const int slot = (ro + k) & (RING - 1);
-                            mu1 += wk * s_ring[ch][0][slot][col]; mu2 += wk * s_ring[ch][1][slot][col];
-                            e11 += wk * s_ring[ch][2][slot][col]; e22 += wk * s_ring[ch][3][slot][col]; e12 += wk * s_ring[ch][4][slot][col];
-                        }
-                        // utils/loss_utils.py:61-74
-                        const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
-                        const float s1 = e11 - mu1_sq, s2 = e22 - mu2_sq, s12 = e12 - mu12;
-                        const float a1 = 2.f * mu12 + C1, a2 = 2.f * s12 + C2, b1 = mu1_sq + mu2_sq + C1, b2 = s1 + s2 + C2;
-                        const float inv = 1.f / (b1 * b2);
-                        const float S = (a1 * a2) * inv;
-                        ssim += S;
+                        float m[5];
+                        taps_col(win, s.ring[ch], ro, t.col, m);
+                        const Ssim q = ssim_of(m);
+                        ssim += q.S;
                         // partial derivatives of S w.r.t. (mu1, E[x^2], E[xy]) with the gt-side moments held fixed
-                        const float dSda1 = a2 * inv, dSda2 = a1 * inv, dSdb1 = -S / b1, dSdb2 = -S / b2;
-                        const float dA = 2.f * mu2 * (dSda1 - dSda2) + 2.f * mu1 * (dSdb1 - dSdb2);
-                        const size_t o = (size_t)(c0 + ch) * HW + (size_t)(y0 + ro) * W + px;
+                        const float dSda1 = q.a2 * q.inv, dSda2 = q.a1 * q.inv, dSdb1 = -q.S / q.b1, dSdb2 = -q.S / q.b2;
+                        const float dA = 2.f * m[1] * (dSda1 - dSda2) + 2.f * m[0] * (dSdb1 - dSdb2);
+                        const size_t o = (size_t)(c0 + ch) * HW + (size_t)(t.y0 + ro) * W + t.px;
                         dmaps[o] = dA;
                         dmaps[(size_t)C * HW + o] = dSdb2;
                         dmaps[2 * (size_t)C * HW + o] = 2.f * dSda2;
                     }
-                    ssim_total += ssim;
-                    if (ssim_errors) {
-                        float *o = ssim_errors + (size_t)(y0 + ro) * W + px;
-                        const float v = first_group ? ssim : *o + ssim;
-                        *o = last_group ? v / (float)C : v;
-                    }
-                }
-                if (it + 1 < n_it) commit(buf ^ 1);
-                __syncthreads();
-            }
+                    sums[1] += ssim;
+                    put_error(ssim_errors, ro, ssim);
+                });
         }
     }
-    // per-workgroup partial sums (no single-address atomics: they serialise ~12 ns each)
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { l1_total += __shfl_xor(l1_total, o, 64); ssim_total += __shfl_xor(ssim_total, o, 64); }
-    if (lane == 0) { s_red[0][wave] = l1_total; s_red[1][wave] = ssim_total; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        partials[2 * blockIdx.x] = s_red[0][0] + s_red[0][1] + s_red[0][2] + s_red[0][3];
-        partials[2 * blockIdx.x + 1] = s_red[1][0] + s_red[1][1] + s_red[1][2] + s_red[1][3];
-    }
+    put_partials(sums, partials);
 }
 
 __global__ __launch_bounds__(256) void l1_ssim_finish_kernel(int nblocks, const float *__restrict__ partials, double inv_count,
     float lambda_dssim, float *__restrict__ loss)
 {
-    __shared__ double s[2][4];
-    double a = 0.0, b = 0.0;
-    for (int i = threadIdx.x; i < nblocks; i += 256) { a += (double)partials[2 * i]; b += (double)partials[2 * i + 1]; }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
-    if (lane == 0) { s[0][wave] = a; s[1][wave] = b; }
-    __syncthreads();
+    double sum[2];
+    sum_partials(nblocks, partials, sum);
     if (threadIdx.x == 0) {
-        const float l1 = (float)((s[0][0] + s[0][1] + s[0][2] + s[0][3]) * inv_count);
-        const float ss = (float)((s[1][0] + s[1][1] + s[1][2] + s[1][3]) * inv_count);
+        const float l1 = (float)(sum[0] * inv_count), ss = (float)(sum[1] * inv_count);
         loss[0] = (1.0f - lambda_dssim) * l1 + lambda_dssim * (1.0f - ss);      // train.py:145
     }
 }
@@ -259,90 +386,45 @@ __global__ __launch_bounds__(256) void l1_ssim_bwd_kernel(int C, int H, int W, c
     float lambda_dssim, float inv_count, float *__restrict__ grad_img, int nsx, int nsy, Table... table)
 {
     constexpr bool kBytes = sizeof...(Table) != 0;
-    __shared__ float s_in[2][3][CG][RPI][SIN + 2];      // [buffer][map A | B | C][channel][row][column]
-    __shared__ float s_ring[CG][3][RING][SW];
+    using St = Stage<3, 3, LH>;                          // maps A | B | C; their three convolutions
+    static_assert(two_workgroups_per_cu<St, 0, Table...>, "l1_ssim_bwd_kernel: two workgroups per CU need <= 80 KB of LDS each");
+    __shared__ St s;
     const int nwork = nsx * nsy;
     const int wi = work_item_of_block(nwork);
     if (wi >= nwork) return;                             // (uniform: the whole workgroup)
     const PixelLds px8 = table_to_lds(table...);        // (read in the column pass, barriers later)
-    const int col = threadIdx.x & (SW - 1), rsub = threadIdx.x >> 6;
     const size_t HW = (size_t)H * W;
     const float gl = grad_loss[0];
-    const int x0 = (wi % nsx) * SW, y0 = (wi / nsx) * SEG;
-    const int rows_out = (H - y0) < SEG ? (H - y0) : SEG;
-    const int n_in = rows_out + 2 * LH;
-    const int n_it = (n_in + RPI - 1) / RPI;
-    const int px = x0 + col;
-    const int hrow = (int)threadIdx.x / (2 * LH), hcol = SW + (int)threadIdx.x % (2 * LH);
-    const bool has_halo = threadIdx.x < RPI * 2 * LH;
+    const Tile<LH, true> t(wi, nsx, H, W);
     for (int c0 = 0; c0 < C; c0 += CG) {
         const int nc = (C - c0) < CG ? (C - c0) : CG;
-        float rm[3 * CG], rh[3 * CG];
-        auto fetch = [&](int it) {
-            const int ym = y0 - LH + it * RPI + rsub, xm = x0 - LH + col;
-            const int yh = y0 - LH + it * RPI + hrow, xh = x0 - LH + hcol;
-            const bool okm = xm >= 0 && xm < W && ym >= 0 && ym < H, okh = has_halo && xh >= 0 && xh < W && yh >= 0 && yh < H;
-            const size_t om = (size_t)ym * W + xm, oh = (size_t)yh * W + xh;
-#pragma unroll
-            for (int pl = 0; pl < 3 * CG; pl++) {
-                const int ch = pl % CG;
-                const float *src = dmaps + ((size_t)(pl / CG) * C + c0 + ch) * HW;
-                rm[pl] = (okm && ch < nc) ? src[om] : 0.f;
-                rh[pl] = (okh && ch < nc) ? src[oh] : 0.f;
-            }
-        };
-        auto commit = [&](int buf) {
-#pragma unroll
-            for (int pl = 0; pl < 3 * CG; pl++) {
-                s_in[buf][pl / CG][pl % CG][rsub][col] = rm[pl];
-                if (has_halo) s_in[buf][pl / CG][pl % CG][hrow][hcol] = rh[pl];
-            }
-        };
-        __syncthreads();
-        fetch(0);
-        commit(0);
-        __syncthreads();
-        for (int it = 0; it < n_it; it++) {
-            const int buf = it & 1;
-            if (it + 1 < n_it) fetch(it + 1);
-            const int rin = it * RPI + rsub;
-            if (rin < n_in) {
+        walk(t, H, W, s, DerivMaps{ dmaps, HW, C, c0, nc },
+            [&](int buf, int rin) {
 #pragma unroll 1
                 for (int ch = 0; ch < nc; ch++) {
-                    const float *sa = &s_in[buf][0][ch][rsub][col], *sb = &s_in[buf][1][ch][rsub][col], *sc = &s_in[buf][2][ch][rsub][col];
-                    float a = 0.f, b = 0.f, cc = 0.f;
+                    const float *sa = &s.in[buf][0][ch][t.rsub][t.col], *sb = &s.in[buf][1][ch][t.rsub][t.col], *sc = &s.in[buf][2][ch][t.rsub][t.col];
+                    float m[3] = { 0.f, 0.f, 0.f };
 #pragma unroll
-                    for (int k = 0; k < EX4D_SSIM_WINDOW; k++) { const float wk = win.w[k]; a += wk * sa[k]; b += wk * sb[k]; cc += wk * sc[k]; }
-                    const int slot = rin & (RING - 1);
-                    s_ring[ch][0][slot][col] = a; s_ring[ch][1][slot][col] = b; s_ring[ch][2][slot][col] = cc;
+                    for (int k = 0; k < EX4D_SSIM_WINDOW; k++) { const float wk = win.w[k]; m[0] += wk * sa[k]; m[1] += wk * sb[k]; m[2] += wk * sc[k]; }
+                    ring_put(s.ring[ch], rin, t.col, m);
                 }
-            }
-            __syncthreads();
-            const int ro = it * RPI + rsub - 2 * LH;
-            if (ro >= 0 && ro < rows_out && px < W) {
-#pragma unroll 1
+            },
+            [&](int ro) {
+#pragma clang loop unroll(disable) vectorize(disable)           // (two channels at a time take 34 registers more)
                 for (int ch = 0; ch < nc; ch++) {
-                    float ca = 0.f, cb = 0.f, ccv = 0.f;
-#pragma unroll
-                    for (int k = 0; k < EX4D_SSIM_WINDOW; k++) {
-                        const float wk = win.w[k];
-                        const int slot = (ro + k) & (RING - 1);
-                        ca += wk * s_ring[ch][0][slot][col]; cb += wk * s_ring[ch][1][slot][col]; ccv += wk * s_ring[ch][2][slot][col];
-                    }
-                    const size_t o = (size_t)(c0 + ch) * HW + (size_t)(y0 + ro) * W + px;
+                    float m[3];
+                    taps_col(win, s.ring[ch], ro, t.col, m);
+                    const size_t o = (size_t)(c0 + ch) * HW + (size_t)(t.y0 + ro) * W + t.px;
                     float yv;
-                    if constexpr (kBytes) yv = px8.v[gt[((size_t)(y0 + ro) * W + px) * px8.S + (c0 + ch)]];
+                    if constexpr (kBytes) yv = px8.v[gt[((size_t)(t.y0 + ro) * W + t.px) * px8.S + (c0 + ch)]];
                     else yv = gt[o];
                     const float xv = img[o];
-                    const float dssim = ca + 2.f * xv * cb + yv * ccv;                   // d(sum of ssim_map)/dx_p
+                    const float dssim = m[0] + 2.f * xv * m[1] + yv * m[2];              // d(sum of ssim_map)/dx_p
                     const float diff = xv - yv;
                     const float sgn = (diff > 0.f) ? 1.f : ((diff < 0.f) ? -1.f : 0.f);  // d|x - y|/dx
                     grad_img[o] = gl * ((1.0f - lambda_dssim) * sgn * inv_count - lambda_dssim * dssim * inv_count);
                 }
-            }
-            if (it + 1 < n_it) commit(buf ^ 1);
-            __syncthreads();
-        }
+            });
     }
 }
 
@@ -352,7 +434,6 @@ __global__ __launch_bounds__(256) void l1_ssim_bwd_kernel(int C, int H, int W, c
 // and the bytes see the clamped value; squared error, non-finite count and the pixel's three bytes come from the centre tap of the
 // row pass, where the L1 term comes from.  Four float partial sums per workgroup (a workgroup has at most 48 x 64 x 3 = 9 216 values:
 // its count is exact in a float); frame_metrics_finish_kernel adds them in double and writes the row.
-static_assert(sizeof(float) * (2 * 2 * CG * RPI * (SIN + 2) + CG * 5 * RING * SW + 16 + 256) <= 80 * 1024, "frame_metrics_kernel: two workgroups per CU need <= 80 KB of LDS each, the table included");
 
 // the 8-bit value of an image value.  Default: torch's mul(255).add_(0.5).clamp_(0, 255).to(uint8) -- product and sum are rounded
 // SEPARATELY, as the two torch kernels round them (this file is compiled with contraction on: the intrinsics never fuse); trunc:
@@ -369,160 +450,64 @@ template <typename T, typename... Table>
 __global__ __launch_bounds__(256) void frame_metrics_kernel(int H, int W, const float *__restrict__ img, const T *__restrict__ gt,
     Window win, int flags, uint8_t *__restrict__ out_u8, float *__restrict__ partials, int nsx, int nsy, Table... table)
 {
-    constexpr bool kBytes = sizeof...(Table) != 0;
-    __shared__ float s_in[2][2][CG][RPI][SIN + 2];      // [buffer][x | y][channel][row][column]
-    __shared__ float s_ring[CG][5][RING][SW];           // row-pass results of the last RING image rows
-    __shared__ float s_red[4][4];
-    const PixelLds px8 = table_to_lds(table...);        // (published by the barrier in front of the first fetch)
+    using St = Stage<2, 5, LH>;                          // maps x | y; five moment maps
+    static_assert(two_workgroups_per_cu<St, 4, Table...>, "frame_metrics_kernel: two workgroups per CU need <= 80 KB of LDS each");
+    __shared__ St s;
+    const PixelLds px8 = table_to_lds(table...);
     const int nwork = nsx * nsy;
     const int wi = work_item_of_block(nwork);
-    const int col = threadIdx.x & (SW - 1), rsub = threadIdx.x >> 6;
-    const size_t HW = (size_t)H * W;
-    const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
     const bool clamp01 = (flags & EX4D_METRICS_CLAMP) != 0, trunc = (flags & EX4D_METRICS_QUANT_TRUNC) != 0;
-    float l1_total = 0.f, sq_total = 0.f, ssim_total = 0.f, bad_total = 0.f;
+    float sums[4] = { 0.f, 0.f, 0.f, 0.f };              // L1, squared error, SSIM, non-finite count
     if (wi < nwork) {
-        const int x0 = (wi % nsx) * SW, y0 = (wi / nsx) * SEG;
-        const int rows_out = (H - y0) < SEG ? (H - y0) : SEG;
-        const int n_in = rows_out + 2 * LH;              // image rows y0 - 5 .. y0 + rows_out + 4
-        const int n_it = (n_in + RPI - 1) / RPI;
-        const int px = x0 + col;
-        const int hrow = (int)threadIdx.x / (2 * LH), hcol = SW + (int)threadIdx.x % (2 * LH);
-        const bool has_halo = threadIdx.x < RPI * 2 * LH;
-        float rm[2 * CG], rh[2 * CG];
-        auto fetch = [&](int it) {
-            const int ym = y0 - LH + it * RPI + rsub, xm = x0 - LH + col;
-            const int yh = y0 - LH + it * RPI + hrow, xh = x0 - LH + hcol;
-            const bool okm = xm >= 0 && xm < W && ym >= 0 && ym < H, okh = has_halo && xh >= 0 && xh < W && yh >= 0 && yh < H;
-            const size_t om = (size_t)ym * W + xm, oh = (size_t)yh * W + xh;
-#pragma unroll
-            for (int pl = 0; pl < 2 * CG; pl++) {
-                const int ch = pl % CG;
-                if constexpr (kBytes) {
-                    if (pl / CG) {                       // the BYTE stays in flight; commit looks it up
-                        rm[pl] = byte_bits(okm, gt, om * px8.S + ch);
-                        rh[pl] = byte_bits(okh, gt, oh * px8.S + ch);
-                        continue;
-                    }
-                }
-                const float *src = ((pl / CG) ? (const float *)gt : img) + (size_t)ch * HW;
-                rm[pl] = okm ? src[om] : 0.f;            // zero padding (conv2d padding=5)
-                rh[pl] = okh ? src[oh] : 0.f;
-            }
-        };
-        auto commit = [&](int buf) {
-#pragma unroll
-            for (int pl = 0; pl < 2 * CG; pl++) {
-                float vm = rm[pl], vh = rh[pl];
-                if (pl / CG) {
-                    if constexpr (kBytes) { vm = byte_value(vm, px8.v); vh = byte_value(vh, px8.v); }
-                } else if (clamp01) {                    // torch.clamp: a NaN stays a NaN (the padding's 0 stays 0)
-                    vm = vm < 0.f ? 0.f : (vm > 1.f ? 1.f : vm);
-                    vh = vh < 0.f ? 0.f : (vh > 1.f ? 1.f : vh);
-                }
-                s_in[buf][pl / CG][pl % CG][rsub][col] = vm;
-                if (has_halo) s_in[buf][pl / CG][pl % CG][hrow][hcol] = vh;
-            }
-        };
-        __syncthreads();                                 // (the table)
-        fetch(0);
-        commit(0);
-        __syncthreads();
-        for (int it = 0; it < n_it; it++) {
-            const int buf = it & 1;
-            if (it + 1 < n_it) fetch(it + 1);            // in flight while this iteration's rows are convolved
-            // ---- row pass of image row rin (relative to y0 - 5) -> ring; when the row lies inside the segment its pixels are output
-            // pixels: their L1 and squared-error terms, their non-finite count and their bytes
-            const int rin = it * RPI + rsub;
-            if (rin < n_in) {
+        const Tile<LH, true> t(wi, nsx, H, W);
+        walk(t, H, W, s, ImagePair<T>{ img, gt, (size_t)H * W, px8, 0, CG, clamp01 },
+            // ---- row pass -> ring; when the row lies inside the segment its pixels are output pixels: their L1 and squared-error
+            // terms, their non-finite count and their bytes
+            [&](int buf, int rin) {
                 const int ro = rin - LH;
-                const bool is_out = ro >= 0 && ro < rows_out && px < W;
-                uint8_t *o8 = (is_out && out_u8) ? out_u8 + ((size_t)(y0 + ro) * W + px) * 3 : nullptr;
+                const bool is_out = t.is_output(ro);
+                uint8_t *o8 = (is_out && out_u8) ? out_u8 + ((size_t)(t.y0 + ro) * W + t.px) * 3 : nullptr;
                 float l1 = 0.f, sq = 0.f, bad = 0.f;
 #pragma unroll 1
                 for (int ch = 0; ch < CG; ch++) {
-                    const float *sx = &s_in[buf][0][ch][rsub][col], *sy = &s_in[buf][1][ch][rsub][col];
-                    float m1 = 0.f, m2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
-#pragma unroll
-                    for (int k = 0; k < EX4D_SSIM_WINDOW; k++) {
-                        const float a = sx[k], b = sy[k], wk = win.w[k];
-                        m1 += wk * a; m2 += wk * b; e11 += wk * (a * a); e22 += wk * (b * b); e12 += wk * (a * b);
-                    }
-                    const int slot = rin & (RING - 1);
-                    s_ring[ch][0][slot][col] = m1; s_ring[ch][1][slot][col] = m2; s_ring[ch][2][slot][col] = e11;
-                    s_ring[ch][3][slot][col] = e22; s_ring[ch][4][slot][col] = e12;
+                    const float *sx = &s.in[buf][0][ch][t.rsub][t.col], *sy = &s.in[buf][1][ch][t.rsub][t.col];
+                    float m[5];
+                    moments_row(win, sx, sy, m);
+                    ring_put(s.ring[ch], rin, t.col, m);
                     const float x = sx[LH], d = x - sy[LH];
                     l1 += fabsf(d);
                     sq += d * d;
                     bad += fabsf(x) <= 3.402823466e+38f ? 0.f : 1.f;          // NaN or +-inf
                     if (o8) o8[ch] = metrics_byte(x, trunc);
                 }
-                if (is_out) { l1_total += l1; sq_total += sq; bad_total += bad; }
-            }
-            __syncthreads();
-            // ---- column pass of output row ro: its window (image rows ro .. ro + 10 relative to y0 - 5) is complete
-            const int ro = it * RPI + rsub - 2 * LH;
-            if (ro >= 0 && ro < rows_out && px < W) {
+                if (is_out) { sums[0] += l1; sums[1] += sq; sums[3] += bad; }
+            },
+            [&](int ro) {
                 float ssim = 0.f;
 #pragma unroll 1
                 for (int ch = 0; ch < CG; ch++) {
-                    float mu1 = 0.f, mu2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
-#pragma unroll
-                    for (int k = 0; k < EX4D_SSIM_WINDOW; k++) {
-                        const float wk = win.w[k];
-                        const int slot = (ro + k) & (RING - 1);
-                        mu1 += wk * s_ring[ch][0][slot][col]; mu2 += wk * s_ring[ch][1][slot][col];
-                        e11 += wk * s_ring[ch][2][slot][col]; e22 += wk * s_ring[ch][3][slot][col]; e12 += wk * s_ring[ch][4][slot][col];
-                    }
-                    // utils/loss_utils.py:61-74, in the forward's order of operations
-                    const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
-                    const float s1 = e11 - mu1_sq, s2 = e22 - mu2_sq, s12 = e12 - mu12;
-                    const float a1 = 2.f * mu12 + C1, a2 = 2.f * s12 + C2, b1 = mu1_sq + mu2_sq + C1, b2 = s1 + s2 + C2;
-                    const float inv = 1.f / (b1 * b2);
-                    ssim += (a1 * a2) * inv;
+                    float m[5];
+                    taps_col(win, s.ring[ch], ro, t.col, m);
+                    ssim += ssim_of(m).S;
                 }
-                ssim_total += ssim;
-            }
-            if (it + 1 < n_it) commit(buf ^ 1);
-            __syncthreads();
-        }
+                sums[2] += ssim;
+            });
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        l1_total += __shfl_xor(l1_total, o, 64); sq_total += __shfl_xor(sq_total, o, 64);
-        ssim_total += __shfl_xor(ssim_total, o, 64); bad_total += __shfl_xor(bad_total, o, 64);
-    }
-    if (lane == 0) { s_red[0][wave] = l1_total; s_red[1][wave] = sq_total; s_red[2][wave] = ssim_total; s_red[3][wave] = bad_total; }
-    __syncthreads();
-    if (threadIdx.x < 4)
-        partials[4 * blockIdx.x + threadIdx.x] = s_red[threadIdx.x][0] + s_red[threadIdx.x][1] + s_red[threadIdx.x][2] + s_red[threadIdx.x][3];
+    put_partials(sums, partials);
 }
 
 __global__ __launch_bounds__(256) void frame_metrics_finish_kernel(int nblocks, const float *__restrict__ partials, double inv_count,
     double *__restrict__ row)
 {
-    __shared__ double s[4][4];
-    double a[4] = { 0.0, 0.0, 0.0, 0.0 };
-    for (int i = threadIdx.x; i < nblocks; i += 256) {
-#pragma unroll
-        for (int q = 0; q < 4; q++) a[q] += (double)partials[4 * i + q];
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) a[q] += __shfl_xor(a[q], o, 64);
-        if (lane == 0) s[q][wave] = a[q];
-    }
-    __syncthreads();
+    double sum[4];
+    sum_partials(nblocks, partials, sum);
     if (threadIdx.x == 0) {
-        const double mse = (s[1][0] + s[1][1] + s[1][2] + s[1][3]) * inv_count;
-        row[0] = (s[0][0] + s[0][1] + s[0][2] + s[0][3]) * inv_count;
+        const double mse = sum[1] * inv_count;
+        row[0] = sum[0] * inv_count;
         row[1] = mse;
         row[2] = 20.0 * log10(1.0 / sqrt(mse));                               // utils/image_utils.py:17-19; +inf at mse 0
-        row[3] = (s[2][0] + s[2][1] + s[2][2] + s[2][3]) * inv_count;
-        row[4] = s[3][0] + s[3][1] + s[3][2] + s[3][3];
+        row[3] = sum[2] * inv_count;
+        row[4] = sum[3];
         row[5] = row[6] = row[7] = 0.0;
     }
 }
@@ -549,12 +534,8 @@ __global__ __launch_bounds__(256) void frame_metrics_finish_kernel(int nblocks, 
 // numerator and denominator are formed by the same float operations in the same order and divided with a correctly rounded division,
 // so equal images score exactly 1.  Three float partial sums per workgroup: sum S(R=1), sum S(R=2), the count of positions whose
 // S(R=1) is not finite (at most 48 x 64 x 3: exact).
-#define SKH 3                       // window half width
-#define SKIN (SW + 2 * SKH)         // 70 input columns of a strip
-#define SKRING 16                   // ring rows (>= EX4D_SKSSIM_WINDOW + RPI - 1, power of two)
-static_assert(EX4D_SKSSIM_WINDOW == 2 * SKH + 1 && SKRING >= EX4D_SKSSIM_WINDOW + RPI - 1 && (SKRING & (SKRING - 1)) == 0, "frame_skssim_kernel: the ring holds a window and an iteration");
-static_assert(RPI * 2 * SKH <= 256, "frame_skssim_kernel: one halo load per thread");
-static_assert(sizeof(float) * (2 * 2 * CG * RPI * (SKIN + 2) + CG * 5 * SKRING * SW + 12 + 256) <= 80 * 1024, "frame_skssim_kernel: two workgroups per CU need <= 80 KB of LDS each, the table included");
+#define SKH 3                       // window half width: 70 input columns of a strip
+static_assert(EX4D_SKSSIM_WINDOW == 2 * SKH + 1, "frame_skssim_kernel: the window is the halo's");
 
 // seven taps of a window, m = their mean, (A, B, C) = the sums of dx^2, dy^2, dx dy about the means (fixed order, explicit rounding)
 __device__ __forceinline__ void sk_centred(const float (&a)[EX4D_SKSSIM_WINDOW], const float (&b)[EX4D_SKSSIM_WINDOW], float &ma, float &mb,
@@ -582,123 +563,57 @@ template <typename T, typename... Table>
 __global__ __launch_bounds__(256) void frame_skssim_kernel(int H, int W, const float *__restrict__ img, const T *__restrict__ gt,
     int flags, float *__restrict__ partials, int nsx, int nsy, Table... table)
 {
-    constexpr bool kBytes = sizeof...(Table) != 0;
-    __shared__ float s_in[2][2][CG][RPI][SKIN + 2];     // [buffer][x | y][channel][row][column]
-    __shared__ float s_ring[CG][5][SKRING][SW];         // row-pass results (mx, my, A, B, C) of the last SKRING image rows
-    __shared__ float s_red[3][4];
-    const PixelLds px8 = table_to_lds(table...);        // (published by the barrier in front of the first fetch)
+    using St = Stage<2, 5, SKH>;                         // maps x | y; row results mx, my, A, B, C
+    static_assert(two_workgroups_per_cu<St, 3, Table...>, "frame_skssim_kernel: two workgroups per CU need <= 80 KB of LDS each");
+    __shared__ St s;
+    const PixelLds px8 = table_to_lds(table...);
     const int nwork = nsx * nsy;
     const int wi = work_item_of_block(nwork);
-    const int col = threadIdx.x & (SW - 1), rsub = threadIdx.x >> 6;
-    const size_t HW = (size_t)H * W;
-    const int Ho = H - 2 * SKH, Wo = W - 2 * SKH;       // the output domain
     const bool clamp01 = (flags & EX4D_METRICS_CLAMP) != 0;
     const float inv_nm1 = 1.0f / 48.0f;                  // sample covariance (scikit-image's default): / (49 - 1)
-    float s1_total = 0.f, s2_total = 0.f, bad_total = 0.f;
+    float sums[3] = { 0.f, 0.f, 0.f };                   // S(R=1), S(R=2), non-finite count
     if (wi < nwork) {
-        const int x0 = (wi % nsx) * SW, y0 = (wi / nsx) * SEG;           // first output column / row = first image column / row read
-        const int rows_out = (Ho - y0) < SEG ? (Ho - y0) : SEG;
-        const int n_in = rows_out + 2 * SKH;             // image rows y0 .. y0 + rows_out + 5
-        const int n_it = (n_in + RPI - 1) / RPI;
-        const int px = x0 + col;                         // this thread's output column
-        const int hrow = (int)threadIdx.x / (2 * SKH), hcol = SW + (int)threadIdx.x % (2 * SKH);
-        const bool has_halo = threadIdx.x < RPI * 2 * SKH;
-        float rm[2 * CG], rh[2 * CG];
-        auto fetch = [&](int it) {
-            const int ym = y0 + it * RPI + rsub, xm = x0 + col;
-            const int yh = y0 + it * RPI + hrow, xh = x0 + hcol;
-            const bool okm = xm < W && ym < H, okh = has_halo && xh < W && yh < H;
-            const size_t om = (size_t)ym * W + xm, oh = (size_t)yh * W + xh;
-#pragma unroll
-            for (int pl = 0; pl < 2 * CG; pl++) {
-                const int ch = pl % CG;
-                if constexpr (kBytes) {
-                    if (pl / CG) {                       // the BYTE stays in flight; commit looks it up
-                        rm[pl] = byte_bits(okm, gt, om * px8.S + ch);
-                        rh[pl] = byte_bits(okh, gt, oh * px8.S + ch);
-                        continue;
-                    }
-                }
-                const float *src = ((pl / CG) ? (const float *)gt : img) + (size_t)ch * HW;
-                rm[pl] = okm ? src[om] : 0.f;            // (beyond the image: read by masked outputs only)
-                rh[pl] = okh ? src[oh] : 0.f;
-            }
-        };
-        auto commit = [&](int buf) {
-#pragma unroll
-            for (int pl = 0; pl < 2 * CG; pl++) {
-                float vm = rm[pl], vh = rh[pl];
-                if (pl / CG) {
-                    if constexpr (kBytes) { vm = byte_value(vm, px8.v); vh = byte_value(vh, px8.v); }
-                } else if (clamp01) {                    // torch.clamp: a NaN stays a NaN
-                    vm = vm < 0.f ? 0.f : (vm > 1.f ? 1.f : vm);
-                    vh = vh < 0.f ? 0.f : (vh > 1.f ? 1.f : vh);
-                }
-                s_in[buf][pl / CG][pl % CG][rsub][col] = vm;
-                if (has_halo) s_in[buf][pl / CG][pl % CG][hrow][hcol] = vh;
-            }
-        };
-        __syncthreads();                                 // (the table)
-        fetch(0);
-        commit(0);
-        __syncthreads();
-        for (int it = 0; it < n_it; it++) {
-            const int buf = it & 1;
-            if (it + 1 < n_it) fetch(it + 1);            // in flight while this iteration's rows are summed
-            // ---- row pass of image row rin (relative to y0): means and centred sums of columns px .. px + 6 -> ring
-            const int rin = it * RPI + rsub;
-            if (rin < n_in) {
-                const int slot = rin & (SKRING - 1);
+        const Tile<SKH, false> t(wi, nsx, H - 2 * SKH, W - 2 * SKH);
+        walk(t, H, W, s, ImagePair<T>{ img, gt, (size_t)H * W, px8, 0, CG, clamp01 },
+            // ---- row pass: means and centred sums of columns px .. px + 6 -> ring
+            [&](int buf, int rin) {
 #pragma unroll 1
                 for (int ch = 0; ch < CG; ch++) {
-                    const float *sx = &s_in[buf][0][ch][rsub][col], *sy = &s_in[buf][1][ch][rsub][col];
-                    float a[EX4D_SKSSIM_WINDOW], b[EX4D_SKSSIM_WINDOW], m1, m2, e11, e22, e12;
+                    const float *sx = &s.in[buf][0][ch][t.rsub][t.col], *sy = &s.in[buf][1][ch][t.rsub][t.col];
+                    float a[EX4D_SKSSIM_WINDOW], b[EX4D_SKSSIM_WINDOW], m[5];
 #pragma unroll
                     for (int k = 0; k < EX4D_SKSSIM_WINDOW; k++) { a[k] = sx[k]; b[k] = sy[k]; }
-                    sk_centred(a, b, m1, m2, e11, e22, e12);
-                    s_ring[ch][0][slot][col] = m1; s_ring[ch][1][slot][col] = m2; s_ring[ch][2][slot][col] = e11;
-                    s_ring[ch][3][slot][col] = e22; s_ring[ch][4][slot][col] = e12;
+                    sk_centred(a, b, m[0], m[1], m[2], m[3], m[4]);
+                    ring_put(s.ring[ch], rin, t.col, m);
                 }
-            }
-            __syncthreads();
-            // ---- column pass of output row ro: its window (image rows ro .. ro + 6 relative to y0) is complete
-            const int ro = it * RPI + rsub - 2 * SKH;
-            if (ro >= 0 && ro < rows_out && px < Wo) {
+            },
+            [&](int ro) {
 #pragma unroll 1
                 for (int ch = 0; ch < CG; ch++) {
                     float a[EX4D_SKSSIM_WINDOW], b[EX4D_SKSSIM_WINDOW], ux, uy, dxx, dyy, dxy;
                     float sxx = 0.f, syy = 0.f, sxy = 0.f;             // (the first add is exact)
 #pragma unroll
                     for (int k = 0; k < EX4D_SKSSIM_WINDOW; k++) {
-                        const int slot = (ro + k) & (SKRING - 1);
-                        a[k] = s_ring[ch][0][slot][col]; b[k] = s_ring[ch][1][slot][col];
-                        sxx = __fadd_rn(sxx, s_ring[ch][2][slot][col]); syy = __fadd_rn(syy, s_ring[ch][3][slot][col]);
-                        sxy = __fadd_rn(sxy, s_ring[ch][4][slot][col]);
+                        const int slot = (ro + k) & (RING - 1);
+                        a[k] = s.ring[ch][0][slot][t.col]; b[k] = s.ring[ch][1][slot][t.col];
+                        sxx = __fadd_rn(sxx, s.ring[ch][2][slot][t.col]); syy = __fadd_rn(syy, s.ring[ch][3][slot][t.col]);
+                        sxy = __fadd_rn(sxy, s.ring[ch][4][slot][t.col]);
                     }
                     sk_centred(a, b, ux, uy, dxx, dyy, dxy);          // the seven row means about the window's mean
-                    const float vx = __fmul_rn(fmaf(7.0f, dxx, sxx), inv_nm1), vy = __fmul_rn(fmaf(7.0f, dyy, syy), inv_nm1);
-                    const float vxy = __fmul_rn(fmaf(7.0f, dxy, sxy), inv_nm1);
-                    const float mxx = __fmul_rn(ux, ux), myy = __fmul_rn(uy, uy), mxy = __fmul_rn(ux, uy);
-                    const float m2xy = __fadd_rn(mxy, mxy), mxxyy = __fadd_rn(mxx, myy), v2xy = __fadd_rn(vxy, vxy), vxxyy = __fadd_rn(vx, vy);
+                    // the four sums of two products, each as ONE product rounded and the other fused into the sum: what contraction
+                    // (on for this file; the rounded-operation intrinsics are plain operators to it) makes of them, stated so that
+                    // the bits do not depend on which products a compiler picks.  Symmetric in x and y where the images are equal
+                    const float txx = fmaf(7.0f, dxx, sxx), tyy = fmaf(7.0f, dyy, syy), txy = fmaf(7.0f, dxy, sxy);
+                    const float m2xy = fmaf(ux, uy, __fmul_rn(ux, uy)), mxxyy = fmaf(uy, uy, __fmul_rn(ux, ux));
+                    const float v2xy = fmaf(txy, inv_nm1, __fmul_rn(txy, inv_nm1)), vxxyy = fmaf(tyy, inv_nm1, __fmul_rn(txx, inv_nm1));
                     const float S1 = sk_s(m2xy, mxxyy, v2xy, vxxyy, 1e-4f, 9e-4f);           // data_range 1: (0.01)^2, (0.03)^2
                     const float S2 = sk_s(m2xy, mxxyy, v2xy, vxxyy, 4e-4f, 3.6e-3f);         // data_range 2: (0.02)^2, (0.06)^2
-                    s1_total += S1; s2_total += S2;
-                    bad_total += fabsf(S1) <= 3.402823466e+38f ? 0.f : 1.f;                  // NaN or +-inf
+                    sums[0] += S1; sums[1] += S2;
+                    sums[2] += fabsf(S1) <= 3.402823466e+38f ? 0.f : 1.f;                    // NaN or +-inf
                 }
-            }
-            if (it + 1 < n_it) commit(buf ^ 1);
-            __syncthreads();
-        }
+            });
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        s1_total += __shfl_xor(s1_total, o, 64); s2_total += __shfl_xor(s2_total, o, 64); bad_total += __shfl_xor(bad_total, o, 64);
-    }
-    if (lane == 0) { s_red[0][wave] = s1_total; s_red[1][wave] = s2_total; s_red[2][wave] = bad_total; }
-    __syncthreads();
-    if (threadIdx.x < 3)
-        partials[3 * blockIdx.x + threadIdx.x] = s_red[threadIdx.x][0] + s_red[threadIdx.x][1] + s_red[threadIdx.x][2] + s_red[threadIdx.x][3];
+    put_partials(sums, partials);
 }
 
 // count: 3 (H-6)(W-6), the same for every channel, so the mean of the channel means is the overall mean; divided, not multiplied by a
@@ -706,24 +621,12 @@ __global__ __launch_bounds__(256) void frame_skssim_kernel(int H, int W, const f
 __global__ __launch_bounds__(256) void frame_skssim_finish_kernel(int nblocks, const float *__restrict__ partials, double count,
     double *__restrict__ row)
 {
-    __shared__ double s[3][4];
-    double a[3] = { 0.0, 0.0, 0.0 };
-    for (int i = threadIdx.x; i < nblocks; i += 256) {
-#pragma unroll
-        for (int q = 0; q < 3; q++) a[q] += (double)partials[3 * i + q];
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < 3; q++) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) a[q] += __shfl_xor(a[q], o, 64);
-        if (lane == 0) s[q][wave] = a[q];
-    }
-    __syncthreads();
+    double sum[3];
+    sum_partials(nblocks, partials, sum);
     if (threadIdx.x == 0) {
-        row[0] = (s[0][0] + s[0][1] + s[0][2] + s[0][3]) / count;
-        row[1] = (s[1][0] + s[1][1] + s[1][2] + s[1][3]) / count;
-        row[2] = s[2][0] + s[2][1] + s[2][2] + s[2][3];
+        row[0] = sum[0] / count;
+        row[1] = sum[1] / count;
+        row[2] = sum[2];
         row[3] = 0.0;
     }
 }
@@ -740,94 +643,103 @@ static inline int strips_of(int W) { return (W + SW - 1) / SW; }
 static inline int segments_of(int H) { return (H + SEG - 1) / SEG; }
 static inline int blocks_of(int H, int W) { return 8 * ((strips_of(W) * segments_of(H) + 7) / 8); }       // (padded: the XCD-aware work-item map)
 
-// the two launches of a forward / the one of a backward, for either kind of ground truth (the arguments were checked by the caller)
-template <typename T, typename... Table>
-int launch_forward(int C, int H, int W, const float *img, const T *gt, float lambda_dssim, const float *window, float *loss,
-                          float *l1_errors, float *ssim_errors, float *dmaps, float *scratch, hipStream_t stream, const Table &... table)
+Window window_of(const float *window)
 {
     Window win;
     for (int i = 0; i < EX4D_SSIM_WINDOW; i++) win.w[i] = window[i];
+    return win;
+}
+
+// what an entry point returns after its launches
+int launched()
+{
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { snprintf(g_loss_err, sizeof(g_loss_err), "launch failed: %s", hipGetErrorString(e)); return EX4D_ERR_HIP; }
+    return EX4D_OK;
+}
+
+// uint8 pixels: the host table (NULL: u / 255, the division PILtoTorch does, utils/general_utils.py:25) as the kernels take it, the
+// trailing argument of a _u8 entry point's call below
+PixelTable pixels_of(int32_t pixel_stride, const float *lut)
+{
+    PixelTable out;
+    out.S = pixel_stride;
+    for (int u = 0; u < 256; u++) out.v[u] = lut ? lut[u] : (float)u / 255.0f;
+    return out;
+}
+
+bool check_pixels(const PixelTable &px)
+{
+    if (px.S == 3 || px.S == 4) return true;
+    snprintf(g_loss_err, sizeof(g_loss_err), "pixel_stride %d: uint8 ground truth has 3 or 4 bytes per pixel", px.S);
+    return false;
+}
+
+// ---- the entry points, for either kind of ground truth: float planes, or uint8 pixels with their table as the trailing argument
+template <typename T, typename... Table>
+int forward(int C, int H, int W, const float *img, const T *gt, float lambda_dssim, const float *window, float *loss, float *l1_errors,
+            float *ssim_errors, float *dmaps, float *scratch, void *stream, const Table &... table)
+{
+    g_loss_err[0] = 0;
+    if (!check_args(C, H, W, img, gt, window) || !loss || !dmaps || !scratch) { snprintf(g_loss_err, sizeof(g_loss_err), "bad argument"); return EX4D_ERR_ARG; }
+    if (!(check_pixels(table) && ...)) return EX4D_ERR_ARG;
     const int nblocks = blocks_of(H, W);
-    hipLaunchKernelGGL((l1_ssim_fwd_kernel<T, Table...>), dim3(nblocks), dim3(256), 0, stream, C, H, W, img, gt, win, l1_errors, ssim_errors, dmaps, scratch,
-                       strips_of(W), segments_of(H), table...);
-    hipLaunchKernelGGL(l1_ssim_finish_kernel, dim3(1), dim3(256), 0, stream, nblocks, scratch,
+    hipLaunchKernelGGL((l1_ssim_fwd_kernel<T, Table...>), dim3(nblocks), dim3(256), 0, (hipStream_t)stream, C, H, W, img, gt, window_of(window), l1_errors,
+                       ssim_errors, dmaps, scratch, strips_of(W), segments_of(H), table...);
+    hipLaunchKernelGGL(l1_ssim_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, nblocks, scratch,
                        1.0 / ((double)C * H * W), lambda_dssim, loss);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { snprintf(g_loss_err, sizeof(g_loss_err), "launch failed: %s", hipGetErrorString(e)); return EX4D_ERR_HIP; }
-    return EX4D_OK;
+    return launched();
 }
 
 template <typename T, typename... Table>
-int launch_backward(int C, int H, int W, const float *img, const T *gt, float lambda_dssim, const float *window, const float *dmaps,
-                           const float *grad_loss, float *grad_img, hipStream_t stream, const Table &... table)
+int backward(int C, int H, int W, const float *img, const T *gt, float lambda_dssim, const float *window, const float *dmaps,
+             const float *grad_loss, float *grad_img, void *stream, const Table &... table)
 {
-    Window win;
-    for (int i = 0; i < EX4D_SSIM_WINDOW; i++) win.w[i] = window[i];
-    hipLaunchKernelGGL((l1_ssim_bwd_kernel<T, Table...>), dim3(blocks_of(H, W)), dim3(256), 0, stream, C, H, W, img, gt, win, dmaps, grad_loss, lambda_dssim,
-                       (float)(1.0 / ((double)C * H * W)), grad_img, strips_of(W), segments_of(H), table...);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { snprintf(g_loss_err, sizeof(g_loss_err), "launch failed: %s", hipGetErrorString(e)); return EX4D_ERR_HIP; }
-    return EX4D_OK;
+    g_loss_err[0] = 0;
+    if (!check_args(C, H, W, img, gt, window) || !dmaps || !grad_loss || !grad_img) { snprintf(g_loss_err, sizeof(g_loss_err), "bad argument"); return EX4D_ERR_ARG; }
+    if (!(check_pixels(table) && ...)) return EX4D_ERR_ARG;
+    hipLaunchKernelGGL((l1_ssim_bwd_kernel<T, Table...>), dim3(blocks_of(H, W)), dim3(256), 0, (hipStream_t)stream, C, H, W, img, gt, window_of(window), dmaps,
+                       grad_loss, lambda_dssim, (float)(1.0 / ((double)C * H * W)), grad_img, strips_of(W), segments_of(H), table...);
+    return launched();
 }
 
-// uint8 pixels + the host table (NULL: u / 255, the division PILtoTorch does, utils/general_utils.py:25) as the kernels take them
-bool pixels_of(const uint8_t *gt, int32_t pixel_stride, const float *lut, PixelTable *out)
+template <typename T, typename... Table>
+int metrics(int H, int W, const float *img, const T *gt, const float *window, int flags, uint8_t *out_u8, double *row, float *scratch,
+            void *stream, const Table &... table)
 {
-    if (!gt || (pixel_stride != 3 && pixel_stride != 4)) {
-        snprintf(g_loss_err, sizeof(g_loss_err), !gt ? "bad argument" : "pixel_stride %d: uint8 ground truth has 3 or 4 bytes per pixel", (int)pixel_stride);
-        return false;
+    g_loss_err[0] = 0;
+    if (!check_args(3, H, W, img, gt, window) || !row || !scratch) { snprintf(g_loss_err, sizeof(g_loss_err), "bad argument"); return EX4D_ERR_ARG; }
+    if (flags & ~(EX4D_METRICS_CLAMP | EX4D_METRICS_QUANT_TRUNC)) {
+        snprintf(g_loss_err, sizeof(g_loss_err), "flags %d: EX4D_METRICS_CLAMP | EX4D_METRICS_QUANT_TRUNC only", flags);
+        return EX4D_ERR_ARG;
     }
-    out->S = pixel_stride;
-    for (int u = 0; u < 256; u++) out->v[u] = lut ? lut[u] : (float)u / 255.0f;
-    return true;
-}
-
-template <typename T, typename... Table>
-int launch_metrics(int H, int W, const float *img, const T *gt, const float *window, int flags, uint8_t *out_u8, double *row,
-                   float *scratch, hipStream_t stream, const Table &... table)
-{
-    Window win;
-    for (int i = 0; i < EX4D_SSIM_WINDOW; i++) win.w[i] = window[i];
+    if (!(check_pixels(table) && ...)) return EX4D_ERR_ARG;
     const int nblocks = blocks_of(H, W);
-    hipLaunchKernelGGL((frame_metrics_kernel<T, Table...>), dim3(nblocks), dim3(256), 0, stream, H, W, img, gt, win, flags, out_u8, scratch,
-                       strips_of(W), segments_of(H), table...);
-    hipLaunchKernelGGL(frame_metrics_finish_kernel, dim3(1), dim3(256), 0, stream, nblocks, scratch, 1.0 / (3.0 * H * W), row);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { snprintf(g_loss_err, sizeof(g_loss_err), "launch failed: %s", hipGetErrorString(e)); return EX4D_ERR_HIP; }
-    return EX4D_OK;
-}
-
-bool check_metrics_args(int H, int W, const void *img, const void *gt, const float *window, int flags, const double *row, const float *scratch)
-{
-    if (!check_args(3, H, W, img, gt, window) || !row || !scratch) { snprintf(g_loss_err, sizeof(g_loss_err), "bad argument"); return false; }
-    if (flags & ~(EX4D_METRICS_CLAMP | EX4D_METRICS_QUANT_TRUNC)) { snprintf(g_loss_err, sizeof(g_loss_err), "flags %d: EX4D_METRICS_CLAMP | EX4D_METRICS_QUANT_TRUNC only", flags); return false; }
-    return true;
+    hipLaunchKernelGGL((frame_metrics_kernel<T, Table...>), dim3(nblocks), dim3(256), 0, (hipStream_t)stream, H, W, img, gt, window_of(window), flags, out_u8,
+                       scratch, strips_of(W), segments_of(H), table...);
+    hipLaunchKernelGGL(frame_metrics_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, nblocks, scratch, 1.0 / (3.0 * H * W), row);
+    return launched();
 }
 
 // scikit-image's SSIM: strips and segments of the output domain (H-6) x (W-6)
 static inline int sk_blocks_of(int H, int W) { return blocks_of(H - 2 * SKH, W - 2 * SKH); }
 
 template <typename T, typename... Table>
-int launch_skssim(int H, int W, const float *img, const T *gt, int flags, double *row, float *scratch, hipStream_t stream, const Table &... table)
+int skssim(int H, int W, const float *img, const T *gt, int flags, double *row, float *scratch, void *stream, const Table &... table)
 {
-    const int Ho = H - 2 * SKH, Wo = W - 2 * SKH, nblocks = sk_blocks_of(H, W);
-    hipLaunchKernelGGL((frame_skssim_kernel<T, Table...>), dim3(nblocks), dim3(256), 0, stream, H, W, img, gt, flags, scratch,
-                       strips_of(Wo), segments_of(Ho), table...);
-    hipLaunchKernelGGL(frame_skssim_finish_kernel, dim3(1), dim3(256), 0, stream, nblocks, scratch, 3.0 * Ho * Wo, row);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { snprintf(g_loss_err, sizeof(g_loss_err), "launch failed: %s", hipGetErrorString(e)); return EX4D_ERR_HIP; }
-    return EX4D_OK;
-}
-
-bool check_skssim_args(int H, int W, const void *img, const void *gt, int flags, const double *row, const float *scratch)
-{
-    if (!img || !gt || !row || !scratch) { snprintf(g_loss_err, sizeof(g_loss_err), "bad argument"); return false; }
+    g_loss_err[0] = 0;
+    if (!img || !gt || !row || !scratch) { snprintf(g_loss_err, sizeof(g_loss_err), "bad argument"); return EX4D_ERR_ARG; }
     if (H < EX4D_SKSSIM_WINDOW || W < EX4D_SKSSIM_WINDOW) {
         snprintf(g_loss_err, sizeof(g_loss_err), "image %d x %d: win_size exceeds image extent (H, W >= %d)", H, W, EX4D_SKSSIM_WINDOW);
-        return false;
+        return EX4D_ERR_ARG;
     }
-    if (flags & ~EX4D_METRICS_CLAMP) { snprintf(g_loss_err, sizeof(g_loss_err), "flags %d: EX4D_METRICS_CLAMP only", flags); return false; }
-    return true;
+    if (flags & ~EX4D_METRICS_CLAMP) { snprintf(g_loss_err, sizeof(g_loss_err), "flags %d: EX4D_METRICS_CLAMP only", flags); return EX4D_ERR_ARG; }
+    if (!(check_pixels(table) && ...)) return EX4D_ERR_ARG;
+    const int Ho = H - 2 * SKH, Wo = W - 2 * SKH, nblocks = sk_blocks_of(H, W);
+    hipLaunchKernelGGL((frame_skssim_kernel<T, Table...>), dim3(nblocks), dim3(256), 0, (hipStream_t)stream, H, W, img, gt, flags, scratch,
+                       strips_of(Wo), segments_of(Ho), table...);
+    hipLaunchKernelGGL(frame_skssim_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, nblocks, scratch, 3.0 * Ho * Wo, row);
+    return launched();
 }
 
 }  // namespace
@@ -849,38 +761,26 @@ int ex4d_l1_ssim_forward(int32_t C, int32_t H, int32_t W, const float *img, cons
                          const float *window, float *loss, float *l1_errors, float *ssim_errors, float *dmaps, float *scratch,
                          void *stream_)
 {
-    g_loss_err[0] = 0;
-    if (!check_args(C, H, W, img, gt, window) || !loss || !dmaps || !scratch) { snprintf(g_loss_err, sizeof(g_loss_err), "bad argument"); return EX4D_ERR_ARG; }
-    return launch_forward(C, H, W, img, gt, lambda_dssim, window, loss, l1_errors, ssim_errors, dmaps, scratch, (hipStream_t)stream_);
-}
-
-int ex4d_l1_ssim_backward(int32_t C, int32_t H, int32_t W, const float *img, const float *gt, float lambda_dssim,
-                          const float *window, const float *dmaps, const float *grad_loss, float *grad_img, void *stream_)
-{
-    g_loss_err[0] = 0;
-    if (!check_args(C, H, W, img, gt, window) || !dmaps || !grad_loss || !grad_img) { snprintf(g_loss_err, sizeof(g_loss_err), "bad argument"); return EX4D_ERR_ARG; }
-    return launch_backward(C, H, W, img, gt, lambda_dssim, window, dmaps, grad_loss, grad_img, (hipStream_t)stream_);
+    return forward(C, H, W, img, gt, lambda_dssim, window, loss, l1_errors, ssim_errors, dmaps, scratch, stream_);
 }
 
 int ex4d_l1_ssim_forward_u8(int32_t H, int32_t W, const float *img, const uint8_t *gt, int32_t pixel_stride, const float *lut,
                             float lambda_dssim, const float *window, float *loss, float *l1_errors, float *ssim_errors, float *dmaps,
                             float *scratch, void *stream_)
 {
-    g_loss_err[0] = 0;
-    PixelTable px;
-    if (!check_args(3, H, W, img, gt, window) || !loss || !dmaps || !scratch) { snprintf(g_loss_err, sizeof(g_loss_err), "bad argument"); return EX4D_ERR_ARG; }
-    if (!pixels_of(gt, pixel_stride, lut, &px)) return EX4D_ERR_ARG;
-    return launch_forward(3, H, W, img, gt, lambda_dssim, window, loss, l1_errors, ssim_errors, dmaps, scratch, (hipStream_t)stream_, px);
+    return forward(3, H, W, img, gt, lambda_dssim, window, loss, l1_errors, ssim_errors, dmaps, scratch, stream_, pixels_of(pixel_stride, lut));
+}
+
+int ex4d_l1_ssim_backward(int32_t C, int32_t H, int32_t W, const float *img, const float *gt, float lambda_dssim,
+                          const float *window, const float *dmaps, const float *grad_loss, float *grad_img, void *stream_)
+{
+    return backward(C, H, W, img, gt, lambda_dssim, window, dmaps, grad_loss, grad_img, stream_);
 }
 
 int ex4d_l1_ssim_backward_u8(int32_t H, int32_t W, const float *img, const uint8_t *gt, int32_t pixel_stride, const float *lut,
                              float lambda_dssim, const float *window, const float *dmaps, const float *grad_loss, float *grad_img, void *stream_)
 {
-    g_loss_err[0] = 0;
-    PixelTable px;
-    if (!check_args(3, H, W, img, gt, window) || !dmaps || !grad_loss || !grad_img) { snprintf(g_loss_err, sizeof(g_loss_err), "bad argument"); return EX4D_ERR_ARG; }
-    if (!pixels_of(gt, pixel_stride, lut, &px)) return EX4D_ERR_ARG;
-    return launch_backward(3, H, W, img, gt, lambda_dssim, window, dmaps, grad_loss, grad_img, (hipStream_t)stream_, px);
+    return backward(3, H, W, img, gt, lambda_dssim, window, dmaps, grad_loss, grad_img, stream_, pixels_of(pixel_stride, lut));
 }
 
 size_t ex4d_frame_metrics_scratch_floats(int32_t H, int32_t W) { return 4 * (size_t)blocks_of(H, W) + 64; }
@@ -888,19 +788,13 @@ size_t ex4d_frame_metrics_scratch_floats(int32_t H, int32_t W) { return 4 * (siz
 int ex4d_frame_metrics(int32_t H, int32_t W, const float *img, const float *gt, const float *window, int32_t flags, uint8_t *out_u8,
                        double *row, float *scratch, void *stream_)
 {
-    g_loss_err[0] = 0;
-    if (!check_metrics_args(H, W, img, gt, window, flags, row, scratch)) return EX4D_ERR_ARG;
-    return launch_metrics(H, W, img, gt, window, flags, out_u8, row, scratch, (hipStream_t)stream_);
+    return metrics(H, W, img, gt, window, flags, out_u8, row, scratch, stream_);
 }
 
 int ex4d_frame_metrics_u8(int32_t H, int32_t W, const float *img, const uint8_t *gt, int32_t pixel_stride, const float *lut,
                           const float *window, int32_t flags, uint8_t *out_u8, double *row, float *scratch, void *stream_)
 {
-    g_loss_err[0] = 0;
-    PixelTable px;
-    if (!check_metrics_args(H, W, img, gt, window, flags, row, scratch)) return EX4D_ERR_ARG;
-    if (!pixels_of(gt, pixel_stride, lut, &px)) return EX4D_ERR_ARG;
-    return launch_metrics(H, W, img, gt, window, flags, out_u8, row, scratch, (hipStream_t)stream_, px);
+    return metrics(H, W, img, gt, window, flags, out_u8, row, scratch, stream_, pixels_of(pixel_stride, lut));
 }
 
 size_t ex4d_frame_skssim_scratch_floats(int32_t H, int32_t W)
@@ -910,19 +804,13 @@ size_t ex4d_frame_skssim_scratch_floats(int32_t H, int32_t W)
 
 int ex4d_frame_skssim(int32_t H, int32_t W, const float *img, const float *gt, int32_t flags, double *row, float *scratch, void *stream_)
 {
-    g_loss_err[0] = 0;
-    if (!check_skssim_args(H, W, img, gt, flags, row, scratch)) return EX4D_ERR_ARG;
-    return launch_skssim(H, W, img, gt, flags, row, scratch, (hipStream_t)stream_);
+    return skssim(H, W, img, gt, flags, row, scratch, stream_);
 }
 
 int ex4d_frame_skssim_u8(int32_t H, int32_t W, const float *img, const uint8_t *gt, int32_t pixel_stride, const float *lut,
                          int32_t flags, double *row, float *scratch, void *stream_)
 {
-    g_loss_err[0] = 0;
-    PixelTable px;
-    if (!check_skssim_args(H, W, img, gt, flags, row, scratch)) return EX4D_ERR_ARG;
-    if (!pixels_of(gt, pixel_stride, lut, &px)) return EX4D_ERR_ARG;
-    return launch_skssim(H, W, img, gt, flags, row, scratch, (hipStream_t)stream_, px);
+    return skssim(H, W, img, gt, flags, row, scratch, stream_, pixels_of(pixel_stride, lut));
 }
 
 }  // extern "C"
