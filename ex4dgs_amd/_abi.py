@@ -166,7 +166,11 @@ PROTOTYPES = {
         _value("ex4d_attributes_last_error", text),
         _status("ex4d_attributes_forward", P(Ex4dAttrParams), *[vp] * 21),
         _status("ex4d_attributes_backward", P(Ex4dAttrParams), *[vp] * 28),
-        _status("ex4d_attributes_backward_sliced", P(Ex4dAttrParams), *[vp] * 27, P(i32), vp))),
+        _status("ex4d_attributes_backward_sliced", P(Ex4dAttrParams), *[vp] * 27, P(i32), vp),
+        _status("ex4d_attr_time_scalars", i32, f64, f64, f64, f64, i32, i32, i32, f64, P(Ex4dAttrParams)),
+        _status("ex4d_attributes_forward_ex", P(Ex4dAttrParams), i32, *[vp] * 21),
+        _status("ex4d_attributes_backward_ex", P(Ex4dAttrParams), i32, *[vp] * 29),
+        _status("ex4d_attributes_backward_sliced_ex", P(Ex4dAttrParams), i32, *[vp] * 28, P(i32), vp))),
     "ex4d_loss.h": ("ex4d_loss_last_error", (
         _value("ex4d_loss_last_error", text),
         _value("ex4d_l1_ssim_scratch_floats", size, i32, i32),
@@ -227,6 +231,7 @@ PROTOTYPES = {
         _status("ex4d_trainer_set_sh_degree", vp, i32),
         _status("ex4d_trainer_set_async", vp, i32),
         _value("ex4d_trainer_replays", i64, vp),
+        _status("ex4d_trainer_set_interp", vp, i32),
         _status("ex4d_trainer_set_regularizers", vp, f64, f64, f64),
         _value("ex4d_trainer_output", vp, vp, i32),
         _value("ex4d_trainer_grad", vp, vp, i32, P(i32)),

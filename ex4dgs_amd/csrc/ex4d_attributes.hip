@@ -5,11 +5,13 @@
 //   CGaussianModel.get_xyz_at_t / get_rotation_at_t      scene/c_gaussian_model.py:170-215
 //   get_scaling / get_features / get_opacity_at_t        scene/c_gaussian_model.py:330-375
 //   cube_interpolate, quat_slerp_interp_uniiterval, time_bigaussian   utils/interpolations.py:81-93, :33-52, :55-61
+//   linear_interp_uniiterval, pchip_interpolate                       utils/interpolations.py:6-7, :65-77
 // and their autograd backward, by two streaming kernels each way: one thread per Gaussian for the 11 floats of
 // (xyz, rotation, opacity, scale), one grid-stride element-wise kernel for the [N,16,3] SH block (the only large
 // stream: 192 B per Gaussian each way).  Static rows first, then dynamic rows (c_gaussian_model.py:193).
 // Compiled with -ffp-contract=off: same float32 operation order as the reference's tensor arithmetic.
 #include "ex4d_internal.h"
+#include <cmath>
 #include <cstdio>
 
 namespace {
@@ -104,6 +106,30 @@ __device__ __forceinline__ void bigaussian_forward(float c0, float c1, float v0,
     b.out = b.inside ? 1.0f : b.o;
 }
 
+// One component of the monotone Hermite slopes (utils/interpolations.py:72-73): a = y[k+1]-y[k], b = y[k]-y[k-1], s = y[k+1]-y[k-1], each
+// its own subtraction; m = a*b > 0 ? (a*b)/s*2 : 0.  The quotient is formed (and, in the adjoint, differentiated) whether kept or not.
+struct PchipSlope { float a, b, s, p; bool keep; };
+
+__device__ __forceinline__ float pchip_slope(float ym, float y0, float yp, PchipSlope &m)
+{
+    m.a = yp - y0; m.b = y0 - ym; m.s = yp - ym;
+    m.p = m.a * m.b;
+    m.keep = m.p > 0.f;
+    const float q = m.p / m.s * 2.0f;
+    return m.keep ? q : 0.f;
+}
+
+// what autograd hands back through where / *2 / div / mul for a slope gradient g_m: the gradients of a, b and s
+__device__ __forceinline__ void pchip_slope_adjoint(const PchipSlope &m, float g_m, float &g_a, float &g_b, float &g_s)
+{
+    const float g_q = (m.keep ? g_m : 0.f) * 2.0f;
+    const float g_p = g_q / m.s;
+    g_s = -g_q * ((m.p / m.s) / m.s);
+    g_a = g_p * m.b;
+    g_b = g_p * m.a;
+}
+
+template <int INTERP>
 __global__ __launch_bounds__(256) void attributes_fwd_kernel(Ex4dAttrParams a,
     const float *__restrict__ xyz, const float *__restrict__ xyz_disp, const float *__restrict__ rotation,
     const float *__restrict__ opacity, const float *__restrict__ scaling,
@@ -126,13 +152,27 @@ __global__ __launch_bounds__(256) void attributes_fwd_kernel(Ex4dAttrParams a,
         for (int c = 0; c < 3; c++) sc[c] = expf(scaling[3 * (size_t)i + c]);
     } else {
         const size_t j = (size_t)(i - a.Ns);
-        // Catmull-Rom Hermite over keyframes k-1..k+2 (interpolations.py:81-93, c_gaussian_model.py:118)
-        const float *y = xyz_motion + (j * a.K + (a.k - 1)) * 3;
+        if (INTERP == EX4D_INTERP_LINEAR) {
+            // keyframes k, k+1 with the weights 1-delta, delta (interpolations.py:6-7, c_gaussian_model.py:107)
+            const float *y = xyz_motion + (j * a.K + a.k) * 3;
 #pragma unroll
-        for (int c = 0; c < 3; c++) {
-            const float y0 = y[c], y1 = y[3 + c], y2 = y[6 + c], y3 = y[9 + c];
-            const float mk = (y2 - y0) / 2.0f, mk1 = (y3 - y1) / 2.0f;
-            m[c] = a.h00 * y1 + a.h10 * mk + a.h01 * y2 + a.h11 * mk1;
+            for (int c = 0; c < 3; c++) m[c] = y[c] * a.h00 + y[3 + c] * a.h01;
+        } else {
+            // Hermite over keyframes k-1..k+2: Catmull-Rom slopes (interpolations.py:81-93, c_gaussian_model.py:118) or the monotone
+            // ones of pchip (interpolations.py:65-77, c_gaussian_model.py:143)
+            const float *y = xyz_motion + (j * a.K + (a.k - 1)) * 3;
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                const float y0 = y[c], y1 = y[3 + c], y2 = y[6 + c], y3 = y[9 + c];
+                float mk, mk1;
+                if (INTERP == EX4D_INTERP_PCHIP) {
+                    PchipSlope s0, s1;
+                    mk = pchip_slope(y0, y1, y2, s0); mk1 = pchip_slope(y1, y2, y3, s1);
+                } else {
+                    mk = (y2 - y0) / 2.0f; mk1 = (y3 - y1) / 2.0f;
+                }
+                m[c] = a.h00 * y1 + a.h10 * mk + a.h01 * y2 + a.h11 * mk1;
+            }
         }
         const float4 *rq = reinterpret_cast<const float4 *>(rotation_motion) + j * a.K + a.k;
         const float4 r1 = rq[0], r2 = rq[1];
@@ -175,8 +215,9 @@ __global__ __launch_bounds__(256) void features_kernel(int Ns, int Nd, float *__
     }
 }
 
+template <int INTERP>
 __global__ __launch_bounds__(256) void attributes_bwd_kernel(Ex4dAttrParams a,
-    const float *__restrict__ opacity, const float *__restrict__ scaling,
+    const float *__restrict__ opacity, const float *__restrict__ scaling, const float *__restrict__ xyz_motion,
     const float *__restrict__ rotation_motion, const float *__restrict__ opacity_motion,
     const float *__restrict__ dur_center, const float *__restrict__ dur_var, const float *__restrict__ scaling_motion,
     const float *__restrict__ g_means3D, const float *__restrict__ g_rotations, const float *__restrict__ g_opacities,
@@ -206,15 +247,39 @@ __global__ __launch_bounds__(256) void attributes_bwd_kernel(Ex4dAttrParams a,
         g_opacity[i] = go * (so * (1.0f - so));
     } else {
         const size_t j = (size_t)(i - a.Ns);
-        // Hermite weights back onto the four keyframes (the other K-4 slices were zero-filled by the host memset)
-        // sliced: g_xyz_motion is [Nd,4,3] (keyframes k-1..k+2), g_rotation_motion [Nd,2,4] (keyframes k, k+1): nothing else exists
-        float *gy = g_xyz_motion + (sliced ? j * 12 : (j * a.K + (a.k - 1)) * 3);
+        // the weights back onto the keyframes of the window (the other slices were zero-filled by the host memset)
+        // sliced: g_xyz_motion is [Nd,4,3] (keyframes k-1..k+2; linear: [Nd,2,3], keyframes k, k+1), g_rotation_motion [Nd,2,4]
+        // (keyframes k, k+1): nothing else exists
+        if (INTERP == EX4D_INTERP_LINEAR) {
+            float *gy = g_xyz_motion + (sliced ? j * 6 : (j * a.K + a.k) * 3);
 #pragma unroll
-        for (int c = 0; c < 3; c++) {
-            gy[c] = -(a.h10 * gm[c]) / 2.0f;
-            gy[3 + c] = a.h00 * gm[c] - (a.h11 * gm[c]) / 2.0f;
-            gy[6 + c] = (a.h10 * gm[c]) / 2.0f + a.h01 * gm[c];
-            gy[9 + c] = (a.h11 * gm[c]) / 2.0f;
+            for (int c = 0; c < 3; c++) { gy[c] = gm[c] * a.h00; gy[3 + c] = gm[c] * a.h01; }
+        } else if (INTERP == EX4D_INTERP_PCHIP) {
+            const float *y = xyz_motion + (j * a.K + (a.k - 1)) * 3;
+            float *gy = g_xyz_motion + (sliced ? j * 12 : (j * a.K + (a.k - 1)) * 3);
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                PchipSlope s0, s1;
+                (void)pchip_slope(y[c], y[3 + c], y[6 + c], s0);
+                (void)pchip_slope(y[3 + c], y[6 + c], y[9 + c], s1);
+                float ga0, gb0, gs0, ga1, gb1, gs1;
+                pchip_slope_adjoint(s0, a.h10 * gm[c], ga0, gb0, gs0);
+                pchip_slope_adjoint(s1, a.h11 * gm[c], ga1, gb1, gs1);
+                // a = y[k+1]-y[k], b = y[k]-y[k-1], s = y[k+1]-y[k-1] of m_k; the same one keyframe on for m_{k+1}
+                gy[c] = -gb0 - gs0;
+                gy[3 + c] = a.h00 * gm[c] + (gb0 - ga0) + (-gb1 - gs1);
+                gy[6 + c] = a.h01 * gm[c] + (ga0 + gs0) + (gb1 - ga1);
+                gy[9 + c] = ga1 + gs1;
+            }
+        } else {
+            float *gy = g_xyz_motion + (sliced ? j * 12 : (j * a.K + (a.k - 1)) * 3);
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                gy[c] = -(a.h10 * gm[c]) / 2.0f;
+                gy[3 + c] = a.h00 * gm[c] - (a.h11 * gm[c]) / 2.0f;
+                gy[6 + c] = (a.h10 * gm[c]) / 2.0f + a.h01 * gm[c];
+                gy[9 + c] = (a.h11 * gm[c]) / 2.0f;
+            }
         }
         const float4 *rq = reinterpret_cast<const float4 *>(rotation_motion) + j * a.K + a.k;
         const float4 r1 = rq[0], r2 = rq[1];
@@ -249,13 +314,69 @@ __global__ __launch_bounds__(256) void attributes_bwd_kernel(Ex4dAttrParams a,
 
 thread_local char g_attr_err[256] = "";
 
+// keyframes the position interpolator reads: k .. k+1 (linear) or k-1 .. k+2 (cube, pchip); the slerp's k, k+1 lie inside both
+bool check_call(const Ex4dAttrParams *a, int32_t interp)
+{
+    if (!a || a->Ns < 0 || a->Nd < 0) { snprintf(g_attr_err, sizeof(g_attr_err), "bad parameters"); return false; }
+    if (interp != EX4D_INTERP_CUBE && interp != EX4D_INTERP_LINEAR && interp != EX4D_INTERP_PCHIP) {
+        snprintf(g_attr_err, sizeof(g_attr_err), "unknown interpolator %d (0 cube, 1 linear, 2 pchip)", (int)interp); return false;
+    }
+    if (a->Nd > 0) {
+        const int before = interp == EX4D_INTERP_LINEAR ? 0 : 1, after = interp == EX4D_INTERP_LINEAR ? 1 : 2;
+        if (a->k < before || (int64_t)a->k + after >= (int64_t)a->K) {
+            snprintf(g_attr_err, sizeof(g_attr_err), "keyframe index %d needs k-%d..k+%d inside [0,%d)", a->k, before, after, a->K); return false;
+        }
+    }
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
 
 const char *ex4d_attributes_last_error(void) { return g_attr_err; }
 
-int ex4d_attributes_forward(const Ex4dAttrParams *a,
+// The Python-number arithmetic of c_gaussian_model.py:184-186, :364 and interpolations.py:7, :83-86 (double precision, then float32):
+// Python's `//` and `%` on floats (floor division; the remainder takes the sign of the divisor, and the quotient is the floor of the
+// exact division except where fmod says otherwise -- float_divmod of CPython), `**` = pow.
+int ex4d_attr_time_scalars(int32_t interp, double duration, double interval, double time_shift, double var_pad,
+                           int32_t Ns, int32_t Nd, int32_t K, double timestamp, Ex4dAttrParams *out)
+{
+    g_attr_err[0] = 0;
+    if (!out) { snprintf(g_attr_err, sizeof(g_attr_err), "no output"); return EX4D_ERR_ARG; }
+    if (interp != EX4D_INTERP_CUBE && interp != EX4D_INTERP_LINEAR && interp != EX4D_INTERP_PCHIP) {
+        snprintf(g_attr_err, sizeof(g_attr_err), "unknown interpolator %d (0 cube, 1 linear, 2 pchip)", (int)interp); return EX4D_ERR_ARG;
+    }
+    Ex4dAttrParams &a = *out;
+    const double tp = timestamp + time_shift;
+    // CPython float_divmod: mod = fmod(vx, wx); div = (vx - mod) / wx; adjust when the signs differ; floordiv = floor(div) rounded
+    double mod = std::fmod(tp, interval);
+    double div = (tp - mod) / interval;
+    if (mod != 0.0) {
+        if ((interval < 0.0) != (mod < 0.0)) { mod += interval; div -= 1.0; }
+    } else {
+        mod = std::copysign(0.0, interval);
+    }
+    double floordiv;
+    if (div != 0.0) { floordiv = std::floor(div); if (div - floordiv > 0.5) floordiv += 1.0; }
+    else floordiv = std::copysign(0.0, tp / interval);
+    const double d = mod / interval;
+    a.Ns = Ns; a.Nd = Nd; a.K = K; a.k = (int32_t)floordiv;
+    a.t = (float)timestamp; a.duration = (float)(duration > 1.0 ? duration : 1.0);
+    a.delta = (float)d;
+    if (interp == EX4D_INTERP_LINEAR) {
+        a.h00 = (float)(1 - d); a.h10 = 0.f; a.h01 = (float)d; a.h11 = 0.f;
+    } else {
+        a.h00 = (float)(2 * std::pow(d, 3) - 3 * std::pow(d, 2) + 1);
+        a.h10 = (float)(std::pow(d, 3) - 2 * std::pow(d, 2) + d);
+        a.h01 = (float)(-2 * std::pow(d, 3) + 3 * std::pow(d, 2));
+        a.h11 = (float)(std::pow(d, 3) - std::pow(d, 2));
+    }
+    a.tau = (float)(tp / interval); a.var_min = (float)(var_pad / interval);
+    return EX4D_OK;
+}
+
+int ex4d_attributes_forward_ex(const Ex4dAttrParams *a, int32_t interp,
     const float *xyz, const float *xyz_disp, const float *rotation, const float *opacity, const float *scaling,
     const float *features_dc, const float *features_rest,
     const float *xyz_motion, const float *rotation_motion, const float *opacity_motion, const float *dur_center,
@@ -264,12 +385,15 @@ int ex4d_attributes_forward(const Ex4dAttrParams *a,
 {
     g_attr_err[0] = 0;
     hipStream_t stream = (hipStream_t)stream_;
-    if (!a || a->Ns < 0 || a->Nd < 0) { snprintf(g_attr_err, sizeof(g_attr_err), "bad parameters"); return EX4D_ERR_ARG; }
+    if (!check_call(a, interp)) return EX4D_ERR_ARG;
     const int N = a->Ns + a->Nd;
     if (N == 0) return EX4D_OK;
-    if (a->Nd > 0 && (a->k < 1 || a->k + 2 >= a->K)) { snprintf(g_attr_err, sizeof(g_attr_err), "keyframe index %d needs k-1..k+2 inside [0,%d)", a->k, a->K); return EX4D_ERR_ARG; }
-    hipLaunchKernelGGL(attributes_fwd_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, *a, xyz, xyz_disp, rotation, opacity, scaling,
-        xyz_motion, rotation_motion, opacity_motion, dur_center, dur_var, scaling_motion, means3D, rotations, opacities, scales);
+#define EX4D_LAUNCH_FWD(I) hipLaunchKernelGGL(attributes_fwd_kernel<I>, dim3((N + 255) / 256), dim3(256), 0, stream, *a, xyz, xyz_disp, rotation, \
+        opacity, scaling, xyz_motion, rotation_motion, opacity_motion, dur_center, dur_var, scaling_motion, means3D, rotations, opacities, scales)
+    if (interp == EX4D_INTERP_LINEAR) EX4D_LAUNCH_FWD(EX4D_INTERP_LINEAR);
+    else if (interp == EX4D_INTERP_PCHIP) EX4D_LAUNCH_FWD(EX4D_INTERP_PCHIP);
+    else EX4D_LAUNCH_FWD(EX4D_INTERP_CUBE);
+#undef EX4D_LAUNCH_FWD
     if (shs) {       // NULL: the caller feeds the rasterizer the four feature tensors directly (Ex4dSplitSH), nothing to gather
         const size_t total = (size_t)N * 12;
         const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
@@ -281,7 +405,7 @@ int ex4d_attributes_forward(const Ex4dAttrParams *a,
     return EX4D_OK;
 }
 
-static int attributes_backward_impl(const Ex4dAttrParams *a, int sliced,
+static int attributes_backward_impl(const Ex4dAttrParams *a, int32_t interp, int sliced, const float *xyz_motion,
     const float *opacity, const float *scaling, const float *rotation_motion, const float *opacity_motion,
     const float *dur_center, const float *dur_var, const float *scaling_motion,
     const float *g_means3D, const float *g_rotations, const float *g_opacities, const float *g_scales, const float *g_shs,
@@ -291,22 +415,28 @@ static int attributes_backward_impl(const Ex4dAttrParams *a, int sliced,
 {
     g_attr_err[0] = 0;
     hipStream_t stream = (hipStream_t)stream_;
-    if (!a || a->Ns < 0 || a->Nd < 0) { snprintf(g_attr_err, sizeof(g_attr_err), "bad parameters"); return EX4D_ERR_ARG; }
+    if (!check_call(a, interp)) return EX4D_ERR_ARG;
     const int N = a->Ns + a->Nd;
     if (N == 0) return EX4D_OK;
     if (a->Nd > 0) {
-        if (a->k < 1 || a->k + 2 >= a->K) { snprintf(g_attr_err, sizeof(g_attr_err), "keyframe index out of range"); return EX4D_ERR_ARG; }
-        // dense gradients of the keyframe tensors: only 4 (xyz) / 2 (rotation) of the K slices are non-zero
+        if (interp == EX4D_INTERP_PCHIP && !xyz_motion) {
+            snprintf(g_attr_err, sizeof(g_attr_err), "the pchip backward reads the keyframe positions: xyz_motion is NULL"); return EX4D_ERR_ARG;
+        }
+        // dense gradients of the keyframe tensors: only 4 or 2 (xyz) / 2 (rotation) of the K slices are non-zero
         if (!sliced && ((((uintptr_t)g_xyz_motion | (uintptr_t)g_rotation_motion) & 15) != 0 ||
             ex4d_launch_zero(g_xyz_motion, (size_t)a->Nd * a->K * 3 * sizeof(float), stream) != hipSuccess ||
             ex4d_launch_zero(g_rotation_motion, (size_t)a->Nd * a->K * 4 * sizeof(float), stream) != hipSuccess)) {
             snprintf(g_attr_err, sizeof(g_attr_err), "clearing the dense keyframe gradients failed (they must be 16-byte aligned)"); return EX4D_ERR_HIP;
         }
     }
-    hipLaunchKernelGGL(attributes_bwd_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, *a, opacity, scaling, rotation_motion, opacity_motion,
-        dur_center, dur_var, scaling_motion, g_means3D, g_rotations, g_opacities, g_scales,
-        g_xyz, g_xyz_disp, g_rotation, g_opacity, g_scaling, g_xyz_motion, g_rotation_motion, g_opacity_motion, g_dur_center, g_dur_var,
-        g_scaling_motion, sliced);
+#define EX4D_LAUNCH_BWD(I) hipLaunchKernelGGL(attributes_bwd_kernel<I>, dim3((N + 255) / 256), dim3(256), 0, stream, *a, opacity, scaling, xyz_motion, \
+        rotation_motion, opacity_motion, dur_center, dur_var, scaling_motion, g_means3D, g_rotations, g_opacities, g_scales, \
+        g_xyz, g_xyz_disp, g_rotation, g_opacity, g_scaling, g_xyz_motion, g_rotation_motion, g_opacity_motion, g_dur_center, g_dur_var, \
+        g_scaling_motion, sliced)
+    if (interp == EX4D_INTERP_LINEAR) EX4D_LAUNCH_BWD(EX4D_INTERP_LINEAR);
+    else if (interp == EX4D_INTERP_PCHIP) EX4D_LAUNCH_BWD(EX4D_INTERP_PCHIP);
+    else EX4D_LAUNCH_BWD(EX4D_INTERP_CUBE);
+#undef EX4D_LAUNCH_BWD
     if (g_shs) {     // NULL: dL/dsh was written into the four gradient tensors by the rasterizer itself (Ex4dSplitSHGrad)
         const size_t total = (size_t)N * 12;
         const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
@@ -318,6 +448,49 @@ static int attributes_backward_impl(const Ex4dAttrParams *a, int sliced,
     return EX4D_OK;
 }
 
+int ex4d_attributes_backward_ex(const Ex4dAttrParams *a, int32_t interp, const float *xyz_motion,
+    const float *opacity, const float *scaling, const float *rotation_motion, const float *opacity_motion,
+    const float *dur_center, const float *dur_var, const float *scaling_motion,
+    const float *g_means3D, const float *g_rotations, const float *g_opacities, const float *g_scales, const float *g_shs,
+    float *g_xyz, float *g_xyz_disp, float *g_rotation, float *g_opacity, float *g_scaling, float *g_features_dc, float *g_features_rest,
+    float *g_xyz_motion, float *g_rotation_motion, float *g_opacity_motion, float *g_dur_center, float *g_dur_var,
+    float *g_scaling_motion, float *g_features_dc_motion, float *g_features_rest_motion, void *stream_)
+{
+    return attributes_backward_impl(a, interp, 0, xyz_motion, opacity, scaling, rotation_motion, opacity_motion, dur_center, dur_var, scaling_motion,
+        g_means3D, g_rotations, g_opacities, g_scales, g_shs, g_xyz, g_xyz_disp, g_rotation, g_opacity, g_scaling, g_features_dc, g_features_rest,
+        g_xyz_motion, g_rotation_motion, g_opacity_motion, g_dur_center, g_dur_var, g_scaling_motion, g_features_dc_motion, g_features_rest_motion, stream_);
+}
+
+int ex4d_attributes_backward_sliced_ex(const Ex4dAttrParams *a, int32_t interp, const float *xyz_motion,
+    const float *opacity, const float *scaling, const float *rotation_motion, const float *opacity_motion,
+    const float *dur_center, const float *dur_var, const float *scaling_motion,
+    const float *g_means3D, const float *g_rotations, const float *g_opacities, const float *g_scales, const float *g_shs,
+    float *g_xyz, float *g_xyz_disp, float *g_rotation, float *g_opacity, float *g_scaling, float *g_features_dc, float *g_features_rest,
+    float *g_xyz_motion_slices, float *g_rotation_motion_slices, float *g_opacity_motion, float *g_dur_center, float *g_dur_var,
+    float *g_scaling_motion, float *g_features_dc_motion, float *g_features_rest_motion, int32_t *slices, void *stream_)
+{
+    if (a && slices) {
+        const bool linear = interp == EX4D_INTERP_LINEAR;
+        slices[0] = linear ? a->k : a->k - 1; slices[1] = linear ? 2 : 4; slices[2] = a->k; slices[3] = 2;
+    }
+    return attributes_backward_impl(a, interp, 1, xyz_motion, opacity, scaling, rotation_motion, opacity_motion, dur_center, dur_var, scaling_motion,
+        g_means3D, g_rotations, g_opacities, g_scales, g_shs, g_xyz, g_xyz_disp, g_rotation, g_opacity, g_scaling, g_features_dc, g_features_rest,
+        g_xyz_motion_slices, g_rotation_motion_slices, g_opacity_motion, g_dur_center, g_dur_var, g_scaling_motion, g_features_dc_motion,
+        g_features_rest_motion, stream_);
+}
+
+int ex4d_attributes_forward(const Ex4dAttrParams *a,
+    const float *xyz, const float *xyz_disp, const float *rotation, const float *opacity, const float *scaling,
+    const float *features_dc, const float *features_rest,
+    const float *xyz_motion, const float *rotation_motion, const float *opacity_motion, const float *dur_center,
+    const float *dur_var, const float *scaling_motion, const float *features_dc_motion, const float *features_rest_motion,
+    float *means3D, float *rotations, float *opacities, float *scales, float *shs, void *stream_)
+{
+    return ex4d_attributes_forward_ex(a, EX4D_INTERP_CUBE, xyz, xyz_disp, rotation, opacity, scaling, features_dc, features_rest, xyz_motion,
+        rotation_motion, opacity_motion, dur_center, dur_var, scaling_motion, features_dc_motion, features_rest_motion,
+        means3D, rotations, opacities, scales, shs, stream_);
+}
+
 int ex4d_attributes_backward(const Ex4dAttrParams *a,
     const float *opacity, const float *scaling, const float *rotation_motion, const float *opacity_motion,
     const float *dur_center, const float *dur_var, const float *scaling_motion,
@@ -326,9 +499,9 @@ int ex4d_attributes_backward(const Ex4dAttrParams *a,
     float *g_xyz_motion, float *g_rotation_motion, float *g_opacity_motion, float *g_dur_center, float *g_dur_var,
     float *g_scaling_motion, float *g_features_dc_motion, float *g_features_rest_motion, void *stream_)
 {
-    return attributes_backward_impl(a, 0, opacity, scaling, rotation_motion, opacity_motion, dur_center, dur_var, scaling_motion, g_means3D, g_rotations,
-        g_opacities, g_scales, g_shs, g_xyz, g_xyz_disp, g_rotation, g_opacity, g_scaling, g_features_dc, g_features_rest, g_xyz_motion,
-        g_rotation_motion, g_opacity_motion, g_dur_center, g_dur_var, g_scaling_motion, g_features_dc_motion, g_features_rest_motion, stream_);
+    return ex4d_attributes_backward_ex(a, EX4D_INTERP_CUBE, nullptr, opacity, scaling, rotation_motion, opacity_motion, dur_center, dur_var, scaling_motion,
+        g_means3D, g_rotations, g_opacities, g_scales, g_shs, g_xyz, g_xyz_disp, g_rotation, g_opacity, g_scaling, g_features_dc, g_features_rest,
+        g_xyz_motion, g_rotation_motion, g_opacity_motion, g_dur_center, g_dur_var, g_scaling_motion, g_features_dc_motion, g_features_rest_motion, stream_);
 }
 
 int ex4d_attributes_backward_sliced(const Ex4dAttrParams *a,
@@ -339,10 +512,10 @@ int ex4d_attributes_backward_sliced(const Ex4dAttrParams *a,
     float *g_xyz_motion_slices, float *g_rotation_motion_slices, float *g_opacity_motion, float *g_dur_center, float *g_dur_var,
     float *g_scaling_motion, float *g_features_dc_motion, float *g_features_rest_motion, int32_t *slices, void *stream_)
 {
-    if (a && slices) { slices[0] = a->k - 1; slices[1] = 4; slices[2] = a->k; slices[3] = 2; }
-    return attributes_backward_impl(a, 1, opacity, scaling, rotation_motion, opacity_motion, dur_center, dur_var, scaling_motion, g_means3D, g_rotations,
-        g_opacities, g_scales, g_shs, g_xyz, g_xyz_disp, g_rotation, g_opacity, g_scaling, g_features_dc, g_features_rest, g_xyz_motion_slices,
-        g_rotation_motion_slices, g_opacity_motion, g_dur_center, g_dur_var, g_scaling_motion, g_features_dc_motion, g_features_rest_motion, stream_);
+    return ex4d_attributes_backward_sliced_ex(a, EX4D_INTERP_CUBE, nullptr, opacity, scaling, rotation_motion, opacity_motion, dur_center, dur_var,
+        scaling_motion, g_means3D, g_rotations, g_opacities, g_scales, g_shs, g_xyz, g_xyz_disp, g_rotation, g_opacity, g_scaling, g_features_dc,
+        g_features_rest, g_xyz_motion_slices, g_rotation_motion_slices, g_opacity_motion, g_dur_center, g_dur_var, g_scaling_motion,
+        g_features_dc_motion, g_features_rest_motion, slices, stream_);
 }
 
 }  // extern "C"

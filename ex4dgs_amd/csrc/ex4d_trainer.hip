@@ -68,6 +68,9 @@ struct Ex4dTrainer {
     int64_t grad_numel[EX4D_TRAINER_PARAMS] = {};
     float *grad[EX4D_TRAINER_PARAMS] = {}, *m[EX4D_TRAINER_PARAMS] = {}, *v[EX4D_TRAINER_PARAMS] = {};
     int32_t slices[4] = { 0, 0, 0, 0 };
+    // position interpolator of the dynamic Gaussians (ex4d_trainer_set_interp); frames counts the steps this handle has run
+    int32_t interp = EX4D_INTERP_CUBE;
+    int64_t frames = 0;
     // per-frame tensors
     float *means3D = nullptr, *rotations = nullptr, *opacities = nullptr, *scales = nullptr;
     float *color = nullptr, *depth = nullptr, *acc = nullptr, *flow = nullptr, *loss = nullptr, *dmaps = nullptr, *loss_scratch = nullptr;
@@ -186,34 +189,11 @@ Ex4dTrainer *ex4d_trainer_create(const Ex4dTrainerConfig *cfg, float *const *par
     return t;
 }
 
-// The Python-number arithmetic of c_gaussian_model.py:184-186, :364 and interpolations.py:83-86 (double precision, then float32):
-// Python's `//` and `%` on floats (floor division; the remainder takes the sign of the divisor, and the quotient is the floor of the
-// exact division except where fmod says otherwise -- float_divmod of CPython), `**` = pow.
+// ex4d_attr_time_scalars for the cube interpolator, from the configuration (the arithmetic lives there)
 void ex4d_trainer_time_scalars(const Ex4dTrainerConfig *cfg, double timestamp, Ex4dAttrParams *out)
 {
     const Ex4dTrainerConfig &c = *cfg;
-    Ex4dAttrParams &a = *out;
-    const double tp = timestamp + c.time_shift;
-    // CPython float_divmod: mod = fmod(vx, wx); div = (vx - mod) / wx; adjust when the signs differ; floordiv = floor(div) rounded
-    double mod = std::fmod(tp, c.interval);
-    double div = (tp - mod) / c.interval;
-    if (mod != 0.0) {
-        if ((c.interval < 0.0) != (mod < 0.0)) { mod += c.interval; div -= 1.0; }
-    } else {
-        mod = std::copysign(0.0, c.interval);
-    }
-    double floordiv;
-    if (div != 0.0) { floordiv = std::floor(div); if (div - floordiv > 0.5) floordiv += 1.0; }
-    else floordiv = std::copysign(0.0, tp / c.interval);
-    const double d = mod / c.interval;
-    a.Ns = c.Ns; a.Nd = c.Nd; a.K = c.K; a.k = (int32_t)floordiv;
-    a.t = (float)timestamp; a.duration = (float)(c.duration > 1.0 ? c.duration : 1.0);
-    a.delta = (float)d;
-    a.h00 = (float)(2 * std::pow(d, 3) - 3 * std::pow(d, 2) + 1);
-    a.h10 = (float)(std::pow(d, 3) - 2 * std::pow(d, 2) + d);
-    a.h01 = (float)(-2 * std::pow(d, 3) + 3 * std::pow(d, 2));
-    a.h11 = (float)(std::pow(d, 3) - std::pow(d, 2));
-    a.tau = (float)(tp / c.interval); a.var_min = (float)(c.var_pad / c.interval);
+    (void)ex4d_attr_time_scalars(EX4D_INTERP_CUBE, c.duration, c.interval, c.time_shift, c.var_pad, c.Ns, c.Nd, c.K, timestamp, out);
 }
 
 int ex4d_trainer_step(Ex4dTrainer *t, double timestamp, const float *viewmatrix, const float *projmatrix, const float *campos,
@@ -255,9 +235,11 @@ static int step_body(Ex4dTrainer *t, double timestamp, const float *viewmatrix, 
     float *const l1_errors = l1_accum ? t->hook + t->HW : nullptr, *const ssim_errors = l1_accum ? t->hook + 2 * t->HW : nullptr;
     const float *const dL_dout_flow = l1_accum ? t->hook : nullptr;
     Ex4dAttrParams a;
-    ex4d_trainer_time_scalars(&c, timestamp, &a);
+    if (ex4d_attr_time_scalars(t->interp, c.duration, c.interval, c.time_shift, c.var_pad, c.Ns, c.Nd, c.K, timestamp, &a))
+        return tfail(EX4D_ERR_ARG, "time scalars: %s", ex4d_attributes_last_error());
+    t->frames += 1;
     float *const *p = t->param;
-    if (ex4d_attributes_forward(&a, p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], p[9], p[10], p[11], p[12], p[13], p[14],
+    if (ex4d_attributes_forward_ex(&a, t->interp, p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], p[9], p[10], p[11], p[12], p[13], p[14],
                                 t->means3D, t->rotations, t->opacities, t->scales, nullptr, stream))
         return tfail(EX4D_ERR_HIP, "attributes forward: %s", ex4d_attributes_last_error());
 
@@ -306,7 +288,7 @@ static int step_body(Ex4dTrainer *t, double timestamp, const float *viewmatrix, 
                                     t->bwd_scratch, stream);
         if (rc) return tfail(rc, "rasterizer backward: %s", ex4d_last_error());
 
-        if (ex4d_attributes_backward_sliced(&a, p[3], p[4], p[8], p[9], p[10], p[11], p[12],
+        if (ex4d_attributes_backward_sliced_ex(&a, t->interp, p[XYZ_MOTION], p[3], p[4], p[8], p[9], p[10], p[11], p[12],
                                             t->g_means3D, t->g_rotations, t->g_opacity, t->g_scales, nullptr,
                                             g[0], g[1], g[2], g[3], g[4], nullptr, nullptr, g[7], g[8], g[9], g[10], g[11], g[12], nullptr, nullptr,
                                             t->slices, stream))
@@ -426,6 +408,19 @@ int ex4d_trainer_set_async(Ex4dTrainer *t, int32_t on)
 }
 
 int64_t ex4d_trainer_replays(const Ex4dTrainer *t) { return t ? t->replays : 0; }
+
+int ex4d_trainer_set_interp(Ex4dTrainer *t, int32_t interp)
+{
+    t_err[0] = 0;
+    if (!t) return tfail(EX4D_ERR_ARG, "null argument");
+    if (interp != EX4D_INTERP_CUBE && interp != EX4D_INTERP_LINEAR && interp != EX4D_INTERP_PCHIP)
+        return tfail(EX4D_ERR_ARG, "unknown interpolator %d (0 cube, 1 linear, 2 pchip)", (int)interp);
+    if (t->frames > 0) return tfail(EX4D_ERR_ARG, "the interpolator is fixed once a step has run: set it right after ex4d_trainer_create");
+    t->interp = interp;
+    // the position window of the sliced keyframe gradient: 2 slices for linear, 4 otherwise (the buffer was taken for 4)
+    t->grad_numel[XYZ_MOTION] = (int64_t)t->cfg.Nd * (interp == EX4D_INTERP_LINEAR ? 2 : 4) * 3;
+    return EX4D_OK;
+}
 
 int ex4d_trainer_set_regularizers(Ex4dTrainer *t, double static_reg, double motion_reg, double rot_reg)
 {

@@ -59,6 +59,8 @@ class NativeTrainer:
         self.handle = None
         self._async, self._reg_w = False, (0.0, 0.0, 0.0)
         self._moments, self._steps = None, 0
+        self.interp_type = getattr(model, "interp_type", "cube")     # kept like the SH degree: every new handle is told again
+        attr.interp_code(self.interp_type)
         self._create()
         self.num_rendered = 0
 
@@ -82,6 +84,7 @@ class NativeTrainer:
             self.handle = lib.ex4d_trainer_create(C.byref(cfg), ptrs)
         if not self.handle:                    # a pointer, not a status: NULL is the refusal
             raise RuntimeError(lib.ex4d_trainer_last_error().decode())
+        _abi.call("ex4d_trainer_set_interp", self.handle, attr.interp_code(self.interp_type))
 
     def step(self, cam, bg, t, gt_image, *, l1_accum=False, stats=None, densify_stats=True, prune_stats=True, apply_optimizer=True,
              nan_census=False, lut=None):
@@ -208,6 +211,13 @@ class NativeTrainer:
         self.cfg.sh_degree = int(degree)
         self.model.active_sh_degree = int(degree)
 
+    def set_interp(self, interp_type):
+        """The position interpolator ('cube', 'linear', 'pchip') of the steps to come; the constructor takes it from the model, so this
+        is for a handle that has not stepped yet -- afterwards the native side refuses (the model's time_shift and keyframe window
+        belong to one interpolator)."""
+        _abi.call("ex4d_trainer_set_interp", self.handle, attr.interp_code(interp_type))
+        self.interp_type = interp_type
+
     def set_async(self, on=True):
         """Asynchronous rasterizer forward (no instance-count read-back in the middle of the frame; include/ex4d_trainer.h):
         same parameters as the synchronous path -- a frame that overflows its capacity is re-run before the optimizer step."""
@@ -238,12 +248,14 @@ class NativeTrainer:
 
     def grad(self, name):
         """Copy of the gradient of parameter `name` of the last step (slices [Nd,4,3] / [Nd,2,4] for the two keyframe tensors) and the
-        slice hint (xyz first keyframe, 4, rotation first keyframe, 2)."""
+        slice hint (xyz first keyframe, 4, rotation first keyframe, 2); under 'linear' the position slices are [Nd,2,3] and the hint
+        says 2."""
         i = self.names.index(name)
         hint = (C.c_int32 * 4)()
         _lib().ex4d_trainer_grad(self.handle, i, hint)
         p = self.params[i]
-        shape = (p.shape[0],) + attr.SLICED_SHAPES[name] if name in attr.SLICED_SHAPES else tuple(p.shape)
+        window = attr.sliced_shapes(self.interp_type)
+        shape = (p.shape[0],) + window[name] if name in window else tuple(p.shape)
         return self._read(100 + i, shape, torch.float32), tuple(int(x) for x in hint)
 
     def _read(self, what, shape, dtype):

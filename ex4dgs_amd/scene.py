@@ -94,6 +94,26 @@ def _cube_interp(y0, y1, y2, y3, d):
     return h00 * y1 + h10 * m_k + h01 * y2 + h11 * m_k1
 
 
+def _linear_interp(y1, y2, d):
+    """utils/interpolations.py:6-7: the two keyframes weighted by the Python numbers 1 - d and d."""
+    return y1 * (1 - d) + y2 * d
+
+
+def _pchip_interp(y0, y1, y2, y3, d):
+    """utils/interpolations.py:65-77: the Hermite basis of _cube_interp with monotone slopes -- where the steps on both sides of a
+    keyframe have the same sign, twice their product over the step across it, else 0.  The quotient is formed on every component
+    (torch.where picks afterwards), so autograd differentiates it where it is dropped too: NaN gradients where y[k+1] == y[k-1]."""
+    h00 = 2 * d ** 3 - 3 * d ** 2 + 1
+    h10 = d ** 3 - 2 * d ** 2 + d
+    h01 = -2 * d ** 3 + 3 * d ** 2
+    h11 = d ** 3 - d ** 2
+
+    def slope(before, at, after):
+        return torch.where((after - at) * (at - before) > 0, (after - at) * (at - before) / (after - before) * 2, torch.zeros_like(at))
+
+    return h00 * y1 + h10 * slope(y0, y1, y2) + h01 * y2 + h11 * slope(y1, y2, y3)
+
+
 def _quat_slerp(qa, qb, frac):
     """Normalised spherical interpolation of two keyframe quaternions with the reference's guards
     (utils/interpolations.py:33-52): cos(angle) clamped to +-(1 - 1e-4), angle / sin / weight-sum floored at 1e-4,
@@ -123,7 +143,9 @@ def _time_bigaussian(centers, log_widths, tau, var_min):
 
 class DynamicGaussians:
     """Parameter container + the five per-frame getters the rasterizer boundary consumes
-    (scene/c_gaussian_model.py:170-215, :330-375; 'cube' xyz interpolation, 'slerp' rotation).
+    (scene/c_gaussian_model.py:170-215, :330-375; xyz interpolation 'cube', 'linear' or 'pchip' -- ModelParams.interp_type --,
+    'slerp' rotation).  The interpolator sets time_shift (time_pad for linear, time_pad + interval otherwise) and with it the
+    keyframe count.  PLY files do not record it, as in the reference: the caller names it again when loading.
 
     Parameter names and shapes follow CGaussianModel: static `_xyz[Ns,3] _xyz_disp[Ns,3] _rotation[Ns,4]
     _opacity[Ns,1] _scaling[Ns,3] _features_dc[Ns,1,3] _features_rest[Ns,15,3]`; dynamic
@@ -132,7 +154,15 @@ class DynamicGaussians:
     """
     PARAM_NAMES = PARAM_ORDER
 
-    def __init__(self, params, duration=300, interval=10, time_pad=2, var_pad=3, kernel_size=0.1, sh_degree=3, fused=False, split_sh=True):
+    def __init__(self, params, duration=300, interval=10, time_pad=2, var_pad=3, kernel_size=0.1, sh_degree=3, fused=False, split_sh=True,
+                 interp_type="cube", rot_interp_type="slerp"):
+        from .attributes import interp_code
+        interp_code(interp_type)                   # ValueError for 'cubic_diff' and unknown names
+        if rot_interp_type != "slerp":
+            raise ValueError(f"rot_interp_type {rot_interp_type!r}: only 'slerp' runs; with 'lerp' the reference itself fails in its "
+                             "constructor, which then never defines the quat_interpolation it assigns (c_gaussian_model.py:150-167)")
+        self.interp_type = interp_type
+        self.rot_interp_type = rot_interp_type
         for n in self.PARAM_NAMES:
             setattr(self, n, params[n])
         # fused=True: the five getters are served by ONE fused HIP evaluation per (timestamp, parameter version)
@@ -144,16 +174,18 @@ class DynamicGaussians:
         self.duration = max(duration, 1)
         self.interval = interval
         self.time_pad = time_pad
-        self.time_shift = time_pad + interval      # c_gaussian_model.py:76,119 ('cube')
+        self.time_shift = time_pad if interp_type == "linear" else time_pad + interval      # c_gaussian_model.py:76,119,144
         self.var_pad = var_pad
         self.kernel_size = kernel_size
         self.active_sh_degree = sh_degree
         self.max_sh_degree = 3
 
     @staticmethod
-    def keyframe_count(duration=300, interval=10, time_pad=2):
-        """c_gaussian_model.py:1254: ceil((duration + time_shift + 2 time_pad + 1)/interval) + 3 (35 for N3V)."""
-        return math.ceil((duration + time_pad + interval + 2 * time_pad + 1) / interval) + 3
+    def keyframe_count(duration=300, interval=10, time_pad=2, interp_type="cube"):
+        """c_gaussian_model.py:1254: ceil((duration + time_shift + 2 time_pad + 1)/interval) + 3 (35 for N3V; 34 under 'linear',
+        whose time_shift lacks the interval)."""
+        time_shift = time_pad if interp_type == "linear" else time_pad + interval
+        return math.ceil((duration + time_shift + 2 * time_pad + 1) / interval) + 3
 
     def parameters(self):
         return [getattr(self, n) for n in self.PARAM_NAMES]
@@ -189,7 +221,8 @@ class DynamicGaussians:
             # "backward through the graph a second time" (several cameras per timestamp, gradient accumulation)
             self._fused_out = evaluate_attributes({n: getattr(self, n) for n in self.PARAM_NAMES}, t, duration=self.duration,
                                                   interval=self.interval, time_shift=self.time_shift, var_pad=self.var_pad,
-                                                  with_shs=not self.split_sh, on_backward=self._drop_fused_cache)
+                                                  with_shs=not self.split_sh, on_backward=self._drop_fused_cache,
+                                                  interp_type=self.interp_type)
             self._fused_key = key
         return self._fused_out
 
@@ -214,7 +247,11 @@ class DynamicGaussians:
             return static
         k, d = self._tk(t)
         y = self._xyz_motion
-        dyn = _cube_interp(y[:, k - 1, :3], y[:, k, :3], y[:, k + 1, :3], y[:, k + 2, :3], d)   # :118
+        if self.interp_type == "linear":
+            dyn = _linear_interp(y[:, k, :], y[:, k + 1, :], d)                                 # :107
+        else:
+            hermite = _pchip_interp if self.interp_type == "pchip" else _cube_interp           # :143, :118
+            dyn = hermite(y[:, k - 1, :3], y[:, k, :3], y[:, k + 1, :3], y[:, k + 2, :3], d)
         return dyn if mode == 2 else torch.cat([static, dyn], dim=0).contiguous()
 
     def get_rotation_at_t(self, t, mode=0):
@@ -309,7 +346,7 @@ CONFIGS = {
 }
 
 
-def make_scene(cfg, P=None, device="cpu", duration=300, fused=False, split_sh=True):
+def make_scene(cfg, P=None, device="cpu", duration=300, fused=False, split_sh=True, interp_type="cube"):
     """Returns (DynamicGaussians, Camera, bg[3]).  Distributions: SURVEY.md 8(d)."""
     if isinstance(cfg, str):
         cfg = CONFIGS[cfg]
@@ -359,7 +396,7 @@ def make_scene(cfg, P=None, device="cpu", duration=300, fused=False, split_sh=Tr
     f_dc = N(P, 1, 3)
     f_rest = 0.15 * N(P, 15, 3)
 
-    K = DynamicGaussians.keyframe_count(duration)
+    K = DynamicGaussians.keyframe_count(duration, interp_type=interp_type)
     params = dict(
         _xyz=xyz[:Ns], _xyz_disp=(0.002 * z[:Ns]).unsqueeze(-1) * N(Ns, 3), _rotation=q[:Ns], _opacity=opacity_logit[:Ns],
         _scaling=torch.log(scale[:Ns]), _features_dc=f_dc[:Ns], _features_rest=f_rest[:Ns])
@@ -372,7 +409,7 @@ def make_scene(cfg, P=None, device="cpu", duration=300, fused=False, split_sh=Tr
         _opacity_duration_center=centers, _opacity_duration_var=N(Nd, 2, 1), _scaling_motion=torch.log(scale[Ns:]),
         _features_dc_motion=f_dc[Ns:], _features_rest_motion=f_rest[Ns:])
     params = {k: v.to(device=device, dtype=torch.float32).contiguous() for k, v in params.items()}
-    model = DynamicGaussians(params, duration=duration, fused=fused, split_sh=split_sh)
+    model = DynamicGaussians(params, duration=duration, fused=fused, split_sh=split_sh, interp_type=interp_type)
     cam = focal_camera(cfg.width, cfg.height, cfg.focal, znear=0.01, zfar=100.0, cxr=cfg.cxr, cyr=cfg.cyr).to(device)
     bg = U(3).to(device)
     return model, cam, bg

@@ -124,7 +124,10 @@ class FrameTrainer:
             raise ValueError("sliced keyframe gradients need an optimizer in the step (plain gradient output is dense)")
         if self.sliced and not fits:
             raise ValueError(f"sliced keyframe gradients take one window per rank, at most {MAX_WINDOWS}")
-        self.kf_idx = [self.names.index(n) for n in attr.SLICED_SHAPES] if self.sliced else []
+        # the model's position interpolator sizes the keyframe window: 2 slices under 'linear', 4 under 'cube' and 'pchip'
+        self.interp_type = getattr(model, "interp_type", "cube")
+        self.sliced_shapes = attr.sliced_shapes(self.interp_type)
+        self.kf_idx = [self.names.index(n) for n in self.sliced_shapes] if self.sliced else []
         self._make_grad_buffers()
         # two exchanges: the four feature gradients (3/4 of the bytes) leave the rasterizer backward and are on the wire while the
         # attribute backward still runs; the other parameters follow it
@@ -133,7 +136,7 @@ class FrameTrainer:
         self.exchange_feat = None
         if self.mode == "sharded":
             self.opt = xdist.ShardedRAdam(self.params, self.lrs, group=group, nan_to_num=[n in NAN_TO_NUM for n in self.names], force=force,
-                                          sliced={i: attr.SLICED_SHAPES[self.names[i]][0] for i in self.kf_idx})
+                                          sliced={i: self.sliced_shapes[self.names[i]][0] for i in self.kf_idx})
             self.exchange = self.opt.exchange
         else:
             if self.mode == "allreduce":
@@ -166,7 +169,7 @@ class FrameTrainer:
         self.pgrad = [None if i in self.feature_idx else torch.zeros_like(p) for i, p in enumerate(self.params)]
         self.kf_gather = []
         for i in self.kf_idx:
-            shape = (self.params[i].shape[0],) + attr.SLICED_SHAPES[self.names[i]]
+            shape = (self.params[i].shape[0],) + self.sliced_shapes[self.names[i]]
             self.pgrad[i] = torch.zeros(shape, dtype=torch.float32, device=self.device)
             if self.mode != "sharded":      # replicated optimizer: every rank needs every window (all-gather); sharded: row all-to-all inside ShardedRAdam
                 self.kf_gather.append(xdist.SliceGather(shape, self.device, group=self._group, local_only=(self.mode != "allreduce"), force=self._force))
@@ -249,9 +252,9 @@ class FrameTrainer:
         m = self.model
         main = torch.cuda.current_stream(self.device)
         scal = attr.time_scalars(t, m.num_static, m.num_dynamic, m._xyz_motion.shape[1] if m.num_dynamic else 0,
-                                 m.duration, m.interval, m.time_shift, m.var_pad)
+                                 m.duration, m.interval, m.time_shift, m.var_pad, self.interp_type)
         with torch.no_grad():
-            xyz, rot, opa, scl, _ = attr.forward_raw(scal, self.params, with_shs=False)
+            xyz, rot, opa, scl, _ = attr.forward_raw(scal, self.params, with_shs=False, interp_type=self.interp_type)
         leaves = [x.requires_grad_(True) for x in (xyz, rot, opa, scl)]
         feats = [self.params[i].detach().requires_grad_(True) for i in self.feature_idx]
         means2D = torch.empty_like(xyz, requires_grad=True)
@@ -287,7 +290,8 @@ class FrameTrainer:
                 self.exchange.wait()                       # previous frame's collectives own the persistent buffers until here
             for gth in self.kf_gather:
                 gth.wait()
-            gout = attr.backward_raw(scal, self.params, (gin[0], gin[1], gin[2], gin[3], None), with_shs=False, out=self.pgrad, sliced=self.sliced)
+            gout = attr.backward_raw(scal, self.params, (gin[0], gin[1], gin[2], gin[3], None), with_shs=False, out=self.pgrad, sliced=self.sliced,
+                                     interp_type=self.interp_type)
             windows = None
             if self.sliced:
                 gout, hint = gout
@@ -374,7 +378,7 @@ class FrameTrainer:
                 sl = []
                 for gth, i in zip(self.kf_gather, self.kf_idx):
                     p = self.params[i]
-                    count, Cc = attr.SLICED_SHAPES[self.names[i]]
+                    count, Cc = self.sliced_shapes[self.names[i]]
                     item = (p.data_ptr(), self.m[i].data_ptr(), self.v[i].data_ptr(), p.shape[0], p.shape[1], Cc, self.lrs[i], self.steps,
                             gth.windows(count), gth.first_device_ptr())
                     if w is not None:

@@ -6,7 +6,9 @@
  *   CGaussianModel.get_xyz_at_t / get_rotation_at_t        scene/c_gaussian_model.py:170-215
  *   get_scaling / get_features / get_opacity_at_t          scene/c_gaussian_model.py:330-375
  *   cube_interpolate / quat_slerp_interp_uniiterval / time_bigaussian   utils/interpolations.py:81-93, :33-52, :55-61
- * ('cube' position interpolation, 'slerp' rotation interpolation: the configuration of configs/N3V and configs/techni).
+ *   linear_interp_uniiterval / pchip_interpolate           utils/interpolations.py:6-7, :65-77
+ * Rotations are interpolated by 'slerp'; positions by the interpolator the caller names (ModelParams.interp_type): 'cube' (the
+ * configuration of configs/N3V and configs/techni; what the entry points without _ex compute), 'linear' or 'pchip'.
  *
  * All pointers are device pointers (float32, contiguous, shapes as in CGaussianModel); `stream` is a hipStream_t.
  * Outputs are [Ns+Nd, ...] with the static rows first (c_gaussian_model.py:193, :215, :374).
@@ -20,16 +22,28 @@
 extern "C" {
 #endif
 
+/* The position interpolator of the dynamic Gaussians (c_gaussian_model.py:98-146).
+ *   CUBE    Catmull-Rom Hermite over keyframes k-1 .. k+2; valid k: 1 .. K-3.
+ *   LINEAR  y[k]*(1-delta) + y[k+1]*delta over keyframes k, k+1; valid k: 0 .. K-2.  Its model has time_shift = time_pad, not
+ *           time_pad + interval.
+ *   PCHIP   Hermite with the monotone slopes m = (a*b > 0) ? (a*b)/s*2 : 0, a = y[k+1]-y[k], b = y[k]-y[k-1], s = y[k+1]-y[k-1];
+ *           keyframes k-1 .. k+2; valid k: 1 .. K-3.  Its backward is the adjoint autograd forms of exactly these operations: the
+ *           quotient is differentiated even where the comparison drops it, so a component with s == 0 exactly (a constant track,
+ *           y[k+1] == y[k-1]) gets NaN gradients on the keyframes the quotient touches, as in the reference.  Such rows go NaN in
+ *           the optimizer and are removed by prune_nan_points, as there. */
+enum { EX4D_INTERP_CUBE = 0, EX4D_INTERP_LINEAR = 1, EX4D_INTERP_PCHIP = 2 };
+
 /* Host-evaluated scalars of one timestamp t (Python numbers in the reference, c_gaussian_model.py:184-186, :364):
  * t' = t + time_shift; k = t' // interval; delta = (t' % interval) / interval; Hermite basis at delta
- * (utils/interpolations.py:83-86, evaluated in double, used as float32); tau = t' / interval; var_min = var_pad / interval. */
+ * (utils/interpolations.py:83-86, evaluated in double, used as float32); tau = t' / interval; var_min = var_pad / interval.
+ * Linear: h00 = 1 - delta, h01 = delta (Python numbers times a float32 tensor, interpolations.py:7), h10 = h11 = 0. */
 typedef struct Ex4dAttrParams {
     int32_t Ns, Nd;            /* static / dynamic Gaussian counts */
     int32_t K;                 /* keyframes per dynamic Gaussian (_xyz_motion.shape[1]) */
-    int32_t k;                 /* keyframe index of this timestamp; slices k-1 .. k+2 are read */
+    int32_t k;                 /* keyframe index of this timestamp; slices k-1 .. k+2 are read (linear: k, k+1) */
     float t, duration;         /* static positions: _xyz + _xyz_disp * t / duration */
     float delta;               /* slerp parameter in [0,1) */
-    float h00, h10, h01, h11;  /* Hermite basis at delta */
+    float h00, h10, h01, h11;  /* Hermite basis at delta (linear: the two weights in h00, h01) */
     float tau;                 /* time in keyframe units for the bi-Gaussian opacity window */
     float var_min;             /* var_pad / interval */
 } Ex4dAttrParams;
@@ -60,9 +74,45 @@ int ex4d_attributes_backward(const Ex4dAttrParams *a,
 /* The same backward with the keyframe gradients as SLICES instead of dense tensors: g_xyz_motion_slices[Nd,4,3] holds the gradients of
  * keyframes slices[0] .. slices[0]+3, g_rotation_motion_slices[Nd,2,4] those of keyframes slices[2], slices[2]+1 -- every other time
  * slice of the dense gradient is zero for this timestamp.  slices = int32[4] {xyz first, xyz count (4), rotation first, rotation count (2)},
- * written on the host (the slice hint an optimizer / gradient exchange needs).  No zero fill of 7 K floats per dynamic Gaussian, and
+ * written on the host (the slice hint an optimizer / gradient exchange needs; this is the cube interpolator's window, see
+ * ex4d_attributes_backward_sliced_ex for the others).  No zero fill of 7 K floats per dynamic Gaussian, and
  * ex4d_radam_step_sliced (ex4d_optim.h) consumes the slices directly. */
 int ex4d_attributes_backward_sliced(const Ex4dAttrParams *a,
+    const float *opacity, const float *scaling, const float *rotation_motion, const float *opacity_motion,
+    const float *opacity_duration_center, const float *opacity_duration_var, const float *scaling_motion,
+    const float *g_means3D, const float *g_rotations, const float *g_opacities, const float *g_scales, const float *g_shs,
+    float *g_xyz, float *g_xyz_disp, float *g_rotation, float *g_opacity, float *g_scaling, float *g_features_dc, float *g_features_rest,
+    float *g_xyz_motion_slices, float *g_rotation_motion_slices, float *g_opacity_motion, float *g_opacity_duration_center,
+    float *g_opacity_duration_var, float *g_scaling_motion, float *g_features_dc_motion, float *g_features_rest_motion,
+    int32_t *slices, void *stream);
+
+/* The scalars of one timestamp for `interp`, from the model's Python numbers: the arithmetic above in double, Python's `//` and `%`.
+ * Pure host code (no GPU needed).  EX4D_ERR_ARG for an unknown interpolator; the keyframe index is checked by the calls below. */
+int ex4d_attr_time_scalars(int32_t interp, double duration, double interval, double time_shift, double var_pad,
+                           int32_t Ns, int32_t Nd, int32_t K, double timestamp, Ex4dAttrParams *out);
+
+/* The three calls above with the position interpolator as an argument (EX4D_INTERP_*); the ones above are these with EX4D_INTERP_CUBE.
+ * An unknown interpolator and a keyframe index outside the interpolator's valid range are refused with EX4D_ERR_ARG before anything
+ * is launched.  The backward calls also take xyz_motion[Nd,K,3]: the pchip adjoint depends on the keyframe positions (it may be NULL
+ * for the other two).  Sliced: the position window is {k, 2} for linear -- g_xyz_motion_slices is [Nd,2,3] -- and {k-1, 4} otherwise;
+ * `slices` says which. */
+int ex4d_attributes_forward_ex(const Ex4dAttrParams *a, int32_t interp,
+    const float *xyz, const float *xyz_disp, const float *rotation, const float *opacity,
+    const float *scaling, const float *features_dc, const float *features_rest,
+    const float *xyz_motion, const float *rotation_motion, const float *opacity_motion,
+    const float *opacity_duration_center, const float *opacity_duration_var,
+    const float *scaling_motion, const float *features_dc_motion, const float *features_rest_motion,
+    float *means3D, float *rotations, float *opacities, float *scales, float *shs, void *stream);
+
+int ex4d_attributes_backward_ex(const Ex4dAttrParams *a, int32_t interp, const float *xyz_motion,
+    const float *opacity, const float *scaling, const float *rotation_motion, const float *opacity_motion,
+    const float *opacity_duration_center, const float *opacity_duration_var, const float *scaling_motion,
+    const float *g_means3D, const float *g_rotations, const float *g_opacities, const float *g_scales, const float *g_shs,
+    float *g_xyz, float *g_xyz_disp, float *g_rotation, float *g_opacity, float *g_scaling, float *g_features_dc, float *g_features_rest,
+    float *g_xyz_motion, float *g_rotation_motion, float *g_opacity_motion, float *g_opacity_duration_center,
+    float *g_opacity_duration_var, float *g_scaling_motion, float *g_features_dc_motion, float *g_features_rest_motion, void *stream);
+
+int ex4d_attributes_backward_sliced_ex(const Ex4dAttrParams *a, int32_t interp, const float *xyz_motion,
     const float *opacity, const float *scaling, const float *rotation_motion, const float *opacity_motion,
     const float *opacity_duration_center, const float *opacity_duration_var, const float *scaling_motion,
     const float *g_means3D, const float *g_rotations, const float *g_opacities, const float *g_scales, const float *g_shs,

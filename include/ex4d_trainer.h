@@ -66,7 +66,8 @@ Ex4dTrainer *ex4d_trainer_create(const Ex4dTrainerConfig *cfg, float *const *par
 void ex4d_trainer_destroy(Ex4dTrainer *t);
 
 /* The host-side scalars of one timestamp exactly as the Python reference computes them (float floor division / modulo / ** in double,
- * then float32) -- what ex4d_trainer_step passes to ex4d_attributes_forward; exported so that the arithmetic can be pinned without a GPU. */
+ * then float32) -- what ex4d_trainer_step passes to ex4d_attributes_forward; exported so that the arithmetic can be pinned without a GPU.
+ * This is ex4d_attr_time_scalars (ex4d_attributes.h) for the cube interpolator; a trainer told another one uses that call with it. */
 struct Ex4dAttrParams;
 void ex4d_trainer_time_scalars(const Ex4dTrainerConfig *cfg, double timestamp, struct Ex4dAttrParams *out);
 
@@ -118,6 +119,12 @@ int ex4d_trainer_set_sh_degree(Ex4dTrainer *t, int32_t degree);
  * again before anything is applied: same parameters as the synchronous path.  ex4d_trainer_replays counts such re-runs. */
 int ex4d_trainer_set_async(Ex4dTrainer *t, int32_t on);
 int64_t ex4d_trainer_replays(const Ex4dTrainer *t);
+/* The position interpolator of the dynamic Gaussians (EX4D_INTERP_* of ex4d_attributes.h; the default is EX4D_INTERP_CUBE): the step
+ * then runs ex4d_attributes_forward_ex / _backward_sliced_ex with it and hands the 2-slice (linear) or 4-slice position window to
+ * ex4d_radam_step_sliced / _reg; gradient 7 is [Nd,2,3] for linear.  The configuration is as before: the caller passes the model's own
+ * time_shift (time_pad for linear, time_pad + interval otherwise).  Allowed before the first step of this handle only: EX4D_ERR_ARG
+ * afterwards and for an unknown value.  A trainer created after density control replaced the tensors is told again. */
+int ex4d_trainer_set_interp(Ex4dTrainer *t, int32_t interp);
 /* Weights of the motion regularisers (ex4d_regularizers.h) from the next step on, as they act at that iteration -- the iteration gates
  * of train.py:156-163 are the caller's (regularizers.regularizer_weights).  All 0 (the default) = off: the sequence above, unchanged.
  * On: ex4d_reg_forward fills output 6, _xyz_disp's term is added to its gradient, the keyframe terms go through
@@ -133,7 +140,7 @@ int ex4d_trainer_set_regularizers(Ex4dTrainer *t, double static_reg, double moti
 const void *ex4d_trainer_output(const Ex4dTrainer *t, int32_t what);
 /* Gradient of parameter i of the last step: dense [shape of the parameter] except i = 7 (_xyz_motion: [Nd,4,3]) and i = 8
  * (_rotation_motion: [Nd,2,4]), the slices of ex4d_attributes_backward_sliced; slices4 (host int32[4], may be NULL) receives
- * {xyz first, 4, rotation first, 2}. */
+ * {xyz first, 4, rotation first, 2}.  Under the linear interpolator gradient 7 is [Nd,2,3] and the hint {xyz first, 2, ...}. */
 const float *ex4d_trainer_grad(const Ex4dTrainer *t, int32_t i, int32_t *slices4);
 /* Asynchronous device-to-device copy of one of the buffers above into caller memory (bindings that cannot wrap a raw pointer):
  * what = 0..8 as in ex4d_trainer_output, 100 + i = gradient of parameter i, 200 + i = exp_avg and 300 + i = exp_avg_sq of parameter i
