@@ -200,6 +200,7 @@ PROTOTYPES = {
         _status("ex4d_dist2", i32, vp, vp, vp, vp))),
     "ex4d_densify.h": ("ex4d_densify_last_error", (
         _status("ex4d_densify_stats", vp, i64, vp, i64, vp, vp, vp, f32, i32, vp),
+        _status("ex4d_densify_stats_merge", vp, vp, i32, i64, vp, vp),
         _status("ex4d_nan_any", vp, i64, vp, i64, vp, vp),
         _value("ex4d_densify_scratch_bytes", size, i64),
         _status("ex4d_densify_plan", i32, P(Ex4dDensifyPlanGroup), vp),

@@ -4,6 +4,7 @@
 // The reference composes these steps from ~40 small torch ops per iteration (train.py:199-216) and, per densify call, three
 // copies of all 15 parameters and both RAdam moments with boolean-mask indexing (a nonzero + host sync each).  Here:
 //   densify_stats   one thread per row, ~100 B per Gaussian, no atomics, no host sync (capturable in a graph)
+//   stats_merge     several ranks: the all-gathered pending blocks folded into the total in rank order, one streaming launch per group
 //   densify_plan    classify (flag byte per row + packed block sums) -> scan of the block sums -> per-row destination map
 //   densify_apply   every source element read once, every destination element written once, descriptors in kernel arguments
 // ffp-contract is off for this file: the threshold decisions and the copied / transformed values follow torch's float32 op order.
@@ -54,6 +55,109 @@ __global__ __launch_bounds__(DN_THREADS) void densify_stats_kernel(float *__rest
     st[EX4D_STAT_ERROR_ACCUM * n + i] = st[EX4D_STAT_ERROR_ACCUM * n + i] + l1;
     st[EX4D_STAT_SSIM_ACCUM * n + i] = st[EX4D_STAT_SSIM_ACCUM * n + i] + e2 / d;
     st[EX4D_STAT_ERROR_DENOM * n + i] = st[EX4D_STAT_ERROR_DENOM * n + i] + (e0 > 0.f ? 1.f : 0.f);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- merge over ranks
+#define DN_MERGE_COLS 4                     // Gaussians per thread and trip: one 16-byte access per statistic row
+#define DN_MERGE_CHUNK (DN_THREADS * DN_MERGE_COLS)    // Gaussians per workgroup and trip
+#define DN_MERGE_MAX_BLOCKS 1024            // 4 waves per SIMD on 256 compute units (the kernel holds two blocks of 36 values per lane); the rest is the grid-stride loop
+
+typedef float merge_f4 __attribute__((ext_vector_type(4)));
+
+// A row of a [9, n] block starts at r n floats: 16-byte aligned for every row only when n % 4 == 0, and the rows of the W + 1 blocks of
+// one call have W + 1 different phases otherwise -- no head / body split aligns them all.  The 16-byte accesses are therefore made at
+// float alignment: global memory on gfx950 takes unaligned wide accesses and the compiler emits global_load_dwordx4 /
+// global_store_dwordx4 for a 4-byte-aligned 16-byte copy (the same machine code as for an aligned one); a wave whose rows are off phase
+// touches 9 cache lines instead of 8.
+__device__ __forceinline__ merge_f4 merge_load(const float *p)
+{
+    merge_f4 v;
+    __builtin_memcpy(&v, p, sizeof(v));
+    return v;
+}
+__device__ __forceinline__ void merge_store(float *p, merge_f4 v) { __builtin_memcpy(p, &v, sizeof(v)); }
+
+__device__ __forceinline__ float stat_init(int r)
+{
+    return r < EX4D_STAT_MIN_RADII ? 0.f : (r == EX4D_STAT_ERROR_MIN_T ? -1.f : 1000.f);
+}
+
+// one Gaussian: the total's nine values t take a rank's nine pending values d (the table of ex4d_densify_stats_merge in the header)
+__device__ __forceinline__ void merge_fold(float (&t)[EX4D_DENSIFY_STATS], const float (&d)[EX4D_DENSIFY_STATS])
+{
+#pragma unroll
+    for (int r = EX4D_STAT_GRAD_ACCUM; r <= EX4D_STAT_ERROR_DENOM; r++) t[r] = t[r] + d[r];
+    t[EX4D_STAT_MAX_RADII] = d[EX4D_STAT_MAX_RADII] > t[EX4D_STAT_MAX_RADII] ? d[EX4D_STAT_MAX_RADII] : t[EX4D_STAT_MAX_RADII];
+    t[EX4D_STAT_MIN_RADII] = d[EX4D_STAT_MIN_RADII] < t[EX4D_STAT_MIN_RADII] ? d[EX4D_STAT_MIN_RADII] : t[EX4D_STAT_MIN_RADII];
+    if (t[EX4D_STAT_ERROR_MIN] > d[EX4D_STAT_ERROR_MIN]) {           // strict, as densify_stats_kernel: a tie keeps the lower rank's, a NaN is never taken
+        t[EX4D_STAT_ERROR_MIN_T] = d[EX4D_STAT_ERROR_MIN_T];
+        t[EX4D_STAT_ERROR_MIN] = d[EX4D_STAT_ERROR_MIN];
+    }
+}
+
+// Left fold of the ranks' pending blocks [world, 9, n] into total [9, n], rank 0 first; own (may be null) is reset to the initial
+// values.  A thread owns four neighbouring Gaussians per trip: it loads their nine rows of the total and of every rank (each a 16-byte
+// access, a rank's nine in flight while the previous rank's are folded), and writes the nine rows back.  The last n % 4 Gaussians go
+// one per thread to the first block.  No thread reads what another writes.
+__global__ __launch_bounds__(DN_THREADS) void stats_merge_kernel(float *__restrict__ total, const float *__restrict__ pending, int world, long long n,
+                                                                  float *__restrict__ own)
+{
+    const long long quads = n >> 2;
+    const long long stride = (long long)gridDim.x * DN_THREADS;
+    for (long long q = (long long)blockIdx.x * DN_THREADS + threadIdx.x; q < quads; q += stride) {
+        const long long c = q << 2;
+        float t[DN_MERGE_COLS][EX4D_DENSIFY_STATS];
+#pragma unroll
+        for (int r = 0; r < EX4D_DENSIFY_STATS; r++) {
+            const merge_f4 v = merge_load(total + r * n + c);
+            t[0][r] = v.x; t[1][r] = v.y; t[2][r] = v.z; t[3][r] = v.w;
+        }
+#pragma unroll 2
+        for (int w = 0; w < world; w++) {
+            const float *p = pending + (long long)w * EX4D_DENSIFY_STATS * n + c;
+            merge_f4 v[EX4D_DENSIFY_STATS];
+#pragma unroll
+            for (int r = 0; r < EX4D_DENSIFY_STATS; r++) v[r] = merge_load(p + r * n);
+            float d[DN_MERGE_COLS][EX4D_DENSIFY_STATS];
+#pragma unroll
+            for (int r = 0; r < EX4D_DENSIFY_STATS; r++) { d[0][r] = v[r].x; d[1][r] = v[r].y; d[2][r] = v[r].z; d[3][r] = v[r].w; }
+#pragma unroll
+            for (int k = 0; k < DN_MERGE_COLS; k++) merge_fold(t[k], d[k]);
+        }
+#pragma unroll
+        for (int r = 0; r < EX4D_DENSIFY_STATS; r++) {
+            merge_f4 v;
+            v.x = t[0][r]; v.y = t[1][r]; v.z = t[2][r]; v.w = t[3][r];
+            merge_store(total + r * n + c, v);
+        }
+        if (own) {
+#pragma unroll
+            for (int r = 0; r < EX4D_DENSIFY_STATS; r++) {
+                const float s = stat_init(r);
+                merge_f4 v;
+                v.x = s; v.y = s; v.z = s; v.w = s;
+                merge_store(own + r * n + c, v);
+            }
+        }
+    }
+    const long long c = (quads << 2) + threadIdx.x;
+    if (blockIdx.x == 0 && c < n) {
+        float t[EX4D_DENSIFY_STATS], d[EX4D_DENSIFY_STATS];
+#pragma unroll
+        for (int r = 0; r < EX4D_DENSIFY_STATS; r++) t[r] = total[r * n + c];
+        for (int w = 0; w < world; w++) {
+            const float *p = pending + (long long)w * EX4D_DENSIFY_STATS * n + c;
+#pragma unroll
+            for (int r = 0; r < EX4D_DENSIFY_STATS; r++) d[r] = p[r * n];
+            merge_fold(t, d);
+        }
+#pragma unroll
+        for (int r = 0; r < EX4D_DENSIFY_STATS; r++) total[r * n + c] = t[r];
+        if (own) {
+#pragma unroll
+            for (int r = 0; r < EX4D_DENSIFY_STATS; r++) own[r * n + c] = stat_init(r);
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------- NaN census
@@ -419,6 +523,31 @@ int ex4d_densify_stats(float *stats_s, int64_t ns, float *stats_d, int64_t nd, c
     if (ns > 0) hipLaunchKernelGGL(densify_stats_kernel, dim3((unsigned)num_blocks(ns)), dim3(DN_THREADS), 0, stream, stats_s, (long long)ns, 0ll, radii, vgrad, egrad, timestamp, (int)flags);
     if (nd > 0) hipLaunchKernelGGL(densify_stats_kernel, dim3((unsigned)num_blocks(nd)), dim3(DN_THREADS), 0, stream, stats_d, (long long)nd, (long long)ns, radii, vgrad, egrad, timestamp, (int)flags);
     return launch_error("densify_stats");
+}
+
+int ex4d_densify_stats_merge(float *total, const float *pending, int32_t world, int64_t n, float *own_pending, void *stream_)
+{
+    g_densify_err[0] = 0;
+    if (world < 0 || n < 0) {
+        snprintf(g_densify_err, sizeof(g_densify_err), "densify_stats_merge: negative rank count or size");
+        return EX4D_ERR_ARG;
+    }
+    if (world == 0 || n == 0) return EX4D_OK;
+    const uintptr_t t0 = (uintptr_t)total, p0 = (uintptr_t)pending, o0 = (uintptr_t)own_pending;
+    const uintptr_t block = (uintptr_t)EX4D_DENSIFY_STATS * (uintptr_t)n * sizeof(float);
+    const uintptr_t t1 = t0 + block, p1 = p0 + block * (uintptr_t)world, o1 = o0 + block;
+    if (!total || !pending || ((t0 | p0 | o0) & 3u)) {
+        snprintf(g_densify_err, sizeof(g_densify_err), "densify_stats_merge: null or misaligned block");
+        return EX4D_ERR_ARG;
+    }
+    if ((t0 < p1 && p0 < t1) || (own_pending && ((o0 < t1 && t0 < o1) || (o0 < p1 && p0 < o1)))) {
+        snprintf(g_densify_err, sizeof(g_densify_err), "densify_stats_merge: the total, the pending blocks and the own block must not overlap");
+        return EX4D_ERR_ARG;
+    }
+    const long long want = ((long long)n + DN_MERGE_CHUNK - 1) / DN_MERGE_CHUNK;
+    const unsigned blocks = (unsigned)(want > DN_MERGE_MAX_BLOCKS ? DN_MERGE_MAX_BLOCKS : want);
+    hipLaunchKernelGGL(stats_merge_kernel, dim3(blocks), dim3(DN_THREADS), 0, (hipStream_t)stream_, total, pending, (int)world, (long long)n, own_pending);
+    return launch_error("densify_stats_merge");
 }
 
 size_t ex4d_densify_scratch_bytes(int64_t n)

@@ -13,10 +13,15 @@ native_trainer.NativeTrainer (its moments read out, a new native handle over the
 the step before it with apply_optimizer=False), or None.
 Random draws are inputs: by default torch.randn on the device (optionally from `generator`), in the reference's draw order; `noise`
 hands in explicit draws.  No CPU fallback: everything runs on a ROCm device.
+
+Several ranks (a FrameTrainer with exchange "allreduce" or "sharded", parameters replicated): DensityStats(model, shared=True) on every
+rank; update() then accumulates the rank's own views, and every call here that changes the rows first merges the ranks' statistics
+(DensityStats.sync), checks that the ranks planned the same counts and uses rank 0's draws -- every rank ends with the same bits.
 """
 import ctypes as C
 
 import torch
+import torch.distributed as dist
 
 from . import _abi
 from ._abi import Ex4dDensifyApplyGroup, Ex4dDensifyPlanGroup, Ex4dDensifyTensor, ptr
@@ -28,6 +33,7 @@ PRUNE_STATS, GRAD_STATS, L1_STATS = 1, 2, 4
 PLAN_DENSIFY, PLAN_PRUNE_INVISIBLE, PLAN_PRUNE_SMALL, PLAN_PRUNE_NAN = 0, 1, 2, 3
 RULE_COPY, RULE_ZERO_NEW, RULE_CONST_NEW, RULE_CHILD_SCALING, RULE_CHILD_XYZ, RULE_CENTER, RULE_STATS = range(7)
 MAX_TENSORS = 24
+MERGE_CHUNK, MERGE_MAX_BLOCKS = 1024, 1024      # DN_MERGE_CHUNK, DN_MERGE_MAX_BLOCKS of ex4d_densify.hip: Gaussians per workgroup and trip, grid cap
 COUNT_NAMES = ("keep", "clone", "keep_clone", "split", "split_clone", "keep_child", "keep_child_clone", "rows")
 
 STATIC_NAMES, DYNAMIC_NAMES = PARAM_ORDER[:7], PARAM_ORDER[7:]       # the static tensors come first
@@ -57,12 +63,21 @@ def densify_thresholds(iteration, opt):
 
 class DensityStats:
     """The densification statistics of a scene.DynamicGaussians (c_gaussian_model.py:408-428 initial values): one [9, Ns] and one
-    [9, Nd] float32 block; the reference-named attributes (xyz_gradient_accum, motion_min_radii2D, ...) are views of them."""
+    [9, Nd] float32 block; the reference-named attributes (xyz_gradient_accum, motion_min_radii2D, ...) are views of them.
 
-    def __init__(self, model, device=None):
+    shared=True (several ranks, each seeing its own views): update() accumulates into a PENDING block per group that starts at
+    STAT_INIT, and sync() all-gathers the ranks' pending blocks and folds them, in rank order, into `static` / `dynamic`
+    (ex4d_densify_stats_merge) -- afterwards the totals are bit-identical on every rank and the pending blocks are at STAT_INIT again.
+    The reference-named attributes read the totals: they are valid after sync().  densify_and_prune, the prunes and
+    growth.extract_dynamic_points sync first, so a pending block is never remapped; after a resize it is fresh at the new size."""
+
+    def __init__(self, model, device=None, shared=False, group=None):
         device = device or model._xyz.device
+        self.shared, self.group = bool(shared), group
         self.static = self._fresh(model.num_static, device)
         self.dynamic = self._fresh(model.num_dynamic, device)
+        self.pending_static = self._fresh(model.num_static, device) if self.shared else None
+        self.pending_dynamic = self._fresh(model.num_dynamic, device) if self.shared else None
 
     @staticmethod
     def _fresh(n, device):
@@ -78,7 +93,8 @@ class DensityStats:
     def update(self, radii, viewspace_grad, error_grad, timestamp, *, densify_stats=True, prune_stats=True, l1_accum=True):
         """One iteration of train.py:199-216: mark_prune_stats (when l1_accum and prune_stats) and, when densify_stats (iteration <
         densify_until_iter), max_radii2D + add_densification_stats + add_l1_ssim_stats (the latter when l1_accum).  radii int32 [P];
-        viewspace_grad = dL/dmeans2D [P, 3]; error_grad = the (e0, e1, e2) hook gradient [P, 3] (None: no error statistics)."""
+        viewspace_grad = dL/dmeans2D [P, 3]; error_grad = the (e0, e1, e2) hook gradient [P, 3] (None: no error statistics).
+        shared: into the pending blocks."""
         ns, nd = self.static.shape[1], self.dynamic.shape[1]
         flags = (GRAD_STATS if densify_stats else 0) | (PRUNE_STATS if (prune_stats and l1_accum) else 0) | \
                 (L1_STATS if (densify_stats and l1_accum) else 0)
@@ -91,9 +107,91 @@ class DensityStats:
                 raise RuntimeError("DensityStats.update: inputs must be contiguous device tensors with one row per Gaussian")
         if radii.dtype != torch.int32 or viewspace_grad.dtype != torch.float32 or (error_grad is not None and error_grad.dtype != torch.float32):
             raise RuntimeError("DensityStats.update: radii int32, gradients float32")
+        blocks = (self.pending_static, self.pending_dynamic) if self.shared else (self.static, self.dynamic)
         with _abi.stream(radii.device) as stream:
-            _abi.call("ex4d_densify_stats", ptr(self.static), ns, ptr(self.dynamic), nd, radii.data_ptr(), viewspace_grad.data_ptr(),
+            _abi.call("ex4d_densify_stats", ptr(blocks[0]), ns, ptr(blocks[1]), nd, radii.data_ptr(), viewspace_grad.data_ptr(),
                       ptr(error_grad), float(timestamp), flags, stream)
+
+    def sync(self, group=None, force=False):
+        """shared: folds every rank's pending blocks into the totals and resets them.  A collective call: every rank of the group makes
+        it at the same point.  Per group of rows one all-gather of the [9, n] pending blocks (all_gather_into_tensor on RCCL, the list
+        form on gloo) and one launch.  In a world of one no collective is issued -- the pending block alone is folded in -- unless
+        `force` (or EX4D_FORCE_COLLECTIVES=1) asks for it: the one-rank collective and the kernel with W = 1, as several ranks run
+        them.  Not shared: nothing to do."""
+        if not self.shared:
+            return
+        from .dist import _backend, _forced
+        group = self.group if group is None else group
+        world = dist.get_world_size(group) if dist.is_initialized() else 1
+        collective = dist.is_initialized() and (world > 1 or _forced(force))
+        for total, pending in ((self.static, self.pending_static), (self.dynamic, self.pending_dynamic)):
+            n = total.shape[1]
+            if n == 0:
+                continue
+            if collective:
+                gathered = torch.empty(world, 9, n, dtype=torch.float32, device=total.device)
+                if _backend(group) == "nccl":
+                    dist.all_gather_into_tensor(gathered, pending, group=group)
+                else:
+                    dist.all_gather([gathered[r] for r in range(world)], pending, group=group)
+            else:
+                gathered = pending.clone().view(1, 9, n)
+            merge_stats(total, gathered, pending)
+
+    def _resized(self, static, dynamic):
+        """The blocks of a new row count (the pending ones were merged before the rows moved: fresh)."""
+        self.static, self.dynamic = static, dynamic
+        if self.shared:
+            self.pending_static = self._fresh(static.shape[1], static.device)
+            self.pending_dynamic = self._fresh(dynamic.shape[1], dynamic.device)
+
+
+def merge_stats(total, pending, own=None):
+    """ex4d_densify_stats_merge on tensors: total [9, n] takes the blocks pending [W, 9, n] in order; own [9, n] (optional) is reset to
+    STAT_INIT.  Contiguous float32 device tensors; no synchronisation."""
+    for t in (total, pending) + ((own,) if own is not None else ()):
+        if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+            raise RuntimeError("merge_stats: contiguous float32 tensors on the device")
+    n = total.shape[-1]
+    if tuple(total.shape) != (9, n) or pending.dim() != 3 or tuple(pending.shape[1:]) != (9, n) or (own is not None and tuple(own.shape) != (9, n)):
+        raise RuntimeError("merge_stats: total [9, n], pending [W, 9, n], own [9, n]")
+    with _abi.stream(total.device) as stream:
+        _abi.call("ex4d_densify_stats_merge", ptr(total), ptr(pending), pending.shape[0], n, ptr(own), stream)
+
+
+# ---------------------------------------------------------------------------------------------------- several ranks
+def _rank_group(stats):
+    """(group, world) when the statistics are shared among several ranks, else (None, 1)."""
+    if getattr(stats, "shared", False) and dist.is_initialized():
+        world = dist.get_world_size(stats.group)
+        if world > 1:
+            return stats.group, world
+    return None, 1
+
+
+def _same_on_every_rank(values, stats, what):
+    """`values` (an integer device tensor, e.g. the plan counts) read back -- after ONE fixed-size collective, the minimum over the
+    ranks of (values, -values), when several ranks share the statistics: a rank whose replica planned different counts would size
+    its tensors and the following collectives differently.  Every rank raises the same RuntimeError then."""
+    group, world = _rank_group(stats)
+    if world == 1:
+        return values.cpu().tolist()
+    v = values.reshape(-1).to(torch.int64)
+    both = torch.cat([v, -v])
+    dist.all_reduce(both, op=dist.ReduceOp.MIN, group=group)
+    both = both.cpu()
+    lo, hi = both[:v.numel()], -both[v.numel():]
+    if not torch.equal(lo, hi):
+        raise RuntimeError(f"{what}: the ranks' replicas disagree (minimum over ranks {lo.tolist()}, maximum {hi.tolist()}): "
+                           "their parameters or statistics are no longer identical")
+    return lo.to(values.dtype).view(values.shape).tolist()
+
+
+def _broadcast(t, stats, src=0):
+    group, world = _rank_group(stats)
+    if world > 1:
+        dist.broadcast(t, src=dist.get_global_rank(group, src) if group is not None else src, group=group)
+    return t
 
 
 # ---------------------------------------------------------------------------------------------------- optimizer adapters
@@ -107,9 +205,12 @@ def _opt_state(opt, params):
         state = opt._moments if opt._moments is not None else opt.begin_density_control()
         return {n: state[n] for n in params}
     if isinstance(opt, FrameTrainer):
-        if not getattr(opt, "optimizer", False) or not hasattr(opt, "m"):
+        if not getattr(opt, "optimizer", False):
             return {n: None for n in params}
         idx = {n: i for i, n in enumerate(opt.names)}
+        if opt.mode == "sharded":                  # the owned ranges move with the rows: the moments whole, gathered from their owners
+            full = opt.opt.full_moments()
+            return {n: full[idx[n]] for n in params}
         return {n: (opt.m[idx[n]], opt.v[idx[n]]) for n in params}
     out = {}
     for n, p in params.items():
@@ -148,11 +249,16 @@ def _rebind(model, opt, new_params, new_moments):
                 opt.state[fresh[name]] = st
 
 
-def _prepare(opt):
+def _prepare(opt, stats=None):
     from .native_trainer import NativeTrainer
     from .trainer import FrameTrainer
+    if isinstance(opt, FrameTrainer) and opt.mode != "none" and opt.world > 1 and stats is not None and not getattr(stats, "shared", False):
+        raise RuntimeError("density control on a multi-rank FrameTrainer needs DensityStats(model, shared=True): every rank would decide on the "
+                           "statistics of its own views and the replicas would part")
     if isinstance(opt, (FrameTrainer, NativeTrainer)):
         opt.begin_density_control()
+    if stats is not None:
+        stats.sync()                               # shared statistics: the decision below reads the merged totals, on every rank the same
 
 
 # ---------------------------------------------------------------------------------------------------- plan + apply
@@ -219,7 +325,7 @@ def _gather(model, stats, opt, plans, counts, rules, groups, names_by_group):
         keep.append(blk)
     _apply(descs, groups, device)
     _rebind(model, opt, new_params, new_moments)
-    stats.static, stats.dynamic = new_blocks
+    stats._resized(*new_blocks)
 
 
 def _groups(plans, counts, noise=None, model=None):
@@ -254,22 +360,33 @@ def _dummy(device):
     return _DUMMY[device]
 
 
-def _draws(counts, has_dynamic, device, generator=None, noise=None):
+def _draws(counts, has_dynamic, device, generator=None, noise=None, stats=None):
     """The standard-normal draws of one densify call, in the reference's order: clone centre jitter (c1, c0) of the dynamic rows,
     static split samples, dynamic split samples, their centre jitter (c1, c0).  `noise` (a dict with the keys of the returned one)
-    overrides; its shapes are checked against the counts."""
+    overrides; its shapes are checked against the counts.  Several ranks sharing `stats`: rank 0 draws (its `noise` and `generator`
+    count), the others receive its draws in one broadcast."""
     nc_d = int(counts[1][1])
     ns_s, ns_d = int(counts[0][3] + counts[0][4]), int(counts[1][3] + counts[1][4])
     shapes = {"clone_c1": (nc_d,), "clone_c0": (nc_d,), "static_split_z": (2 * ns_s, 3), "split_z": (2 * ns_d, 3),
               "split_c1": (2 * ns_d,), "split_c0": (2 * ns_d,)}
     order = ("clone_c1", "clone_c0", "static_split_z", "split_z", "split_c1", "split_c0") if has_dynamic else ("static_split_z",)
     out = {}
+    group, world = _rank_group(stats)
+    drawing = world == 1 or dist.get_rank(group) == 0
     for k in order:
-        if noise is not None and k in noise:
+        if not drawing:
+            t = torch.empty(shapes[k], dtype=torch.float32, device=device)
+        elif noise is not None and k in noise:
             t = noise[k].to(device=device, dtype=torch.float32).contiguous().reshape(shapes[k])
         else:
             t = torch.randn(shapes[k], device=device, generator=generator)
         out[k] = t
+    if world > 1:
+        flat = _broadcast(torch.cat([out[k].reshape(-1) for k in order]), stats)
+        off = 0
+        for k in order:
+            out[k] = flat[off:off + out[k].numel()].view(shapes[k]).clone()
+            off += out[k].numel()
     for k in shapes:
         out.setdefault(k, torch.zeros(shapes[k], device=device))
     return out
@@ -281,7 +398,7 @@ def densify_and_prune(model, stats, opt, max_grad, max_dgrad, min_opacity, min_m
     """CGaussianModel.densify_and_prune (:1019): clone, split, postfix resets, prune -- one plan per group, ONE read-back of the
     counts, one multi-tensor gather.  Returns {"static": counts, "dynamic": counts, "draws": the draws used} with counts keyed by
     COUNT_NAMES.  Nd == 0: the dynamic state is left untouched (densification_postfix_onlystatic)."""
-    _prepare(opt)
+    _prepare(opt, stats)
     device = model._xyz.device
     ns, nd = model.num_static, model.num_dynamic
     f32 = lambda x: float(torch.tensor(x, dtype=torch.float32))
@@ -293,8 +410,9 @@ def densify_and_prune(model, stats, opt, max_grad, max_dgrad, min_opacity, min_m
     plans = [_plan(PLAN_DENSIFY, stats.static, ns, device, model._scaling.detach(), model._opacity.detach(), thr=thr_s),
              _plan(PLAN_DENSIFY, stats.dynamic, nd, device, model._scaling_motion.detach(), model._opacity_motion.detach(), thr=thr_d)
              if nd > 0 else None]
-    counts = torch.stack([plans[0][1], plans[1][1] if plans[1] is not None else torch.zeros_like(plans[0][1])]).cpu().tolist()   # the one read-back
-    draws = _draws(counts, nd > 0, device, generator, noise)
+    counts = _same_on_every_rank(torch.stack([plans[0][1], plans[1][1] if plans[1] is not None else torch.zeros_like(plans[0][1])]),
+                                 stats, "densify_and_prune")                                 # the one read-back
+    draws = _draws(counts, nd > 0, device, generator, noise, stats)
     noise_g = [{"split_z": draws["static_split_z"]},
                {k: draws[k] for k in ("split_z", "split_c1", "split_c0", "clone_c1", "clone_c0")}]
     groups = _groups(plans, counts, noise_g, model)
@@ -310,12 +428,13 @@ def densify_and_prune(model, stats, opt, max_grad, max_dgrad, min_opacity, min_m
 
 
 def _prune(mode, model, stats, opt):
-    _prepare(opt)
+    _prepare(opt, stats)
     device = model._xyz.device
     ns, nd = model.num_static, model.num_dynamic
     plans = [_plan(mode, stats.static, ns, device, xyz=model._xyz.detach()),
              _plan(mode, stats.dynamic, nd, device, xyz=model._xyz_motion.detach()) if nd > 0 else None]
-    counts = torch.stack([plans[0][1], plans[1][1] if plans[1] is not None else torch.zeros_like(plans[0][1])]).cpu().tolist()
+    counts = _same_on_every_rank(torch.stack([plans[0][1], plans[1][1] if plans[1] is not None else torch.zeros_like(plans[0][1])]),
+                                 stats, "prune")
     groups = _groups(plans, counts)
     # prune_points returns before the dynamic half when it is empty (c_gaussian_model.py:737-738)
     _gather(model, stats, opt, plans, counts, {}, groups, [STATIC_NAMES, DYNAMIC_NAMES if nd > 0 else ()])

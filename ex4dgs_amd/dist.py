@@ -466,6 +466,47 @@ class ShardedRAdam:
     def state_bytes(self):
         return 8 * sum(hi - lo for lo, hi in self.owned)
 
+    def full_moments(self):
+        """[(exp_avg, exp_avg_sq)] with the parameters' shapes, whole on every rank: a small tensor's moments are whole already (views of
+        the state), a large one's owned ranges are all-gathered and the last rank's tail broadcast -- the collectives of step()'s
+        parameter all-gather.  A collective call.  For callers that change the rows (ex4dgs_amd.densify): the owned element ranges move
+        with the row count, so the moments are remapped whole and handed to the new optimizer's load_moments."""
+        out = []
+        for i, p in enumerate(self.params):
+            pair = []
+            for state in (self.exp_avg[i], self.exp_avg_sq[i]):
+                n = p.numel()
+                if self.small[i] or not (self.world > 1 or self.force):
+                    pair.append(state.view(p.shape))
+                    continue
+                full = torch.empty(n, dtype=torch.float32, device=self.device)
+                lo, hi, s = shard_range(n, self.rank, self.world, align=self.align[i])
+                if s > 0:
+                    if self._native:
+                        dist.all_gather_into_tensor(full[:self.world * s], state[:s].contiguous(), group=self.group)
+                    else:
+                        dist.all_gather([full[r * s:(r + 1) * s] for r in range(self.world)], state[:s].contiguous(), group=self.group)
+                if self.world * s < n:            # the tail lives behind the last rank's slice
+                    if self.rank == self.world - 1:
+                        full[self.world * s:].copy_(state[s:])
+                    src = self.world - 1
+                    dist.broadcast(full[self.world * s:], src=dist.get_global_rank(self.group, src) if self.group is not None else src, group=self.group)
+                pair.append(full.view(p.shape))
+            out.append(tuple(pair))
+        return out
+
+    def load_moments(self, moments):
+        """moments: per parameter (exp_avg, exp_avg_sq) with the parameter's shape, the same on every rank, or None (zeros): every rank
+        keeps its owned range.  No collective."""
+        assert len(moments) == len(self.params)
+        for i, (pair, (lo, hi)) in enumerate(zip(moments, self.owned)):
+            if pair is None:
+                self.exp_avg[i].zero_(); self.exp_avg_sq[i].zero_()
+                continue
+            for state, full in zip((self.exp_avg[i], self.exp_avg_sq[i]), pair):
+                assert full.numel() == self.params[i].numel()
+                state.copy_(full.reshape(-1)[lo:hi])
+
     def launch_exchange(self, grads, windows=None):
         """Start the gradient reduce-scatter (asynchronous); step() waits for it.  grads: one entry per parameter (the entries of
         sliced tensors are ignored); windows: {tensor index: (window [rows, count, C], first keyframe)} for the sliced tensors."""

@@ -17,10 +17,12 @@ import ctypes as C
 import math
 
 import torch
+import torch.distributed as dist
 
 from . import _abi
 from ._abi import Ex4dDensifyApplyGroup, Ex4dGrowthAppend, Ex4dGrowthClassify, Ex4dGrowthTensor, ptr
-from .densify import (DYNAMIC_NAMES, STATIC_NAMES, COUNT_NAMES, RULE_COPY, _apply, _desc, _opt_state, _prepare, _rebind)
+from .densify import (DYNAMIC_NAMES, STATIC_NAMES, COUNT_NAMES, RULE_COPY, _apply, _broadcast, _desc, _opt_state, _prepare, _rebind,
+                      _same_on_every_rank)
 
 GROW_COPY, GROW_ZERO, GROW_XYZ, GROW_ROTATION, GROW_CENTER, GROW_VAR, GROW_STATS = range(7)
 MAX_TENSORS = 28
@@ -37,18 +39,45 @@ _STATIC_SOURCE = {"_opacity_motion": "_opacity", "_scaling_motion": "_scaling", 
 class ErrorTimestamps:
     """mark_error / get_errorneous_timestamp (:1299-1328): the summed loss and the count per keyframe interval; pop() returns the
     middle of the interval with the largest mean loss among those seen more than a tenth as often as the most frequent one SO FAR
-    (the running maximum follows the dict's insertion order, as the reference's loop does), and forgets that interval."""
+    (the running maximum follows the dict's insertion order, as the reference's loop does), and forgets that interval.
 
-    def __init__(self, interval):
+    shared=True (several ranks, each marking the losses of its own views): mark() logs locally; sync() gathers the ranks' logs and
+    replays them in (mark index, rank) order -- the i-th marks of ranks 0 .. W-1, then the (i+1)-th -- so every rank holds the dict,
+    insertion order included, of one process that saw the views in that order.  pop() syncs first; both are collective calls.  A loss
+    travels as a float64 (a Python float, or a tensor's item())."""
+
+    def __init__(self, interval, shared=False, group=None):
         self.interval = interval
         self.errors = {}
+        self.shared, self.group = bool(shared), group
+        self._log = []
 
     def mark(self, loss, timestamp):
+        if self.shared:
+            self._log.append((float(loss), timestamp))
+        else:
+            self._apply(loss, timestamp)
+
+    def _apply(self, loss, timestamp):
         idx = timestamp // self.interval
         total, count = self.errors.get(idx, (0, 0))
         self.errors[idx] = (total + loss, count + 1) if count else (loss, 1)
 
+    def sync(self):
+        if not self.shared:
+            return
+        logs = [self._log]
+        if dist.is_initialized() and dist.get_world_size(self.group) > 1:
+            logs = [None] * dist.get_world_size(self.group)
+            dist.all_gather_object(logs, self._log, group=self.group)
+        self._log = []
+        for i in range(max(len(l) for l in logs)):
+            for l in logs:
+                if i < len(l):
+                    self._apply(*l[i])
+
     def pop(self):
+        self.sync()
         best_loss, best_idx, most = 0, 0, 0
         for idx, (total, count) in self.errors.items():
             most = max(most, count)
@@ -112,7 +141,7 @@ def _append(descs, args, device):
 
 
 def extract_dynamic_points(model, stats, opt, viewpoint_loc, timestamp, vis_filter, extent, percentile=0.98, motion_thres=1000.0,
-                           min_motion_thres=1e-6, max_dur=None):
+                           min_motion_thres=1e-6, max_dur=None, src=0):
     """CGaussianModel.extract_dynamic_points_from_static (:1147): the visible static rows whose normalised motion score is above its
     `percentile` quantile (or whose displacement is above motion_thres * extent), that move at all (min_motion_thres * extent) and
     have been seen (error-min timestamp >= 0) become dynamic rows, appended after the existing ones in ascending source order, and
@@ -122,8 +151,10 @@ def extract_dynamic_points(model, stats, opt, viewpoint_loc, timestamp, vis_filt
     group counts the new rows), "threshold": the quantile as a float, "visible": the visible rows}.  With no visible row the reference
     raises inside max / quantile; here the call changes nothing and returns zero counts.  With visible rows and none selected the
     state keeps its values except the dynamic accumulators, which are reset as the reference resets them ("reset grad anyway");
-    an all-static model stays as it is."""
-    _prepare(opt)
+    an all-static model stays as it is.
+    Several ranks sharing `stats` (DensityStats(shared=True)): the statistics are merged first, and the camera position and the
+    visibility filter are those of rank `src`, broadcast -- every rank extracts the same rows."""
+    _prepare(opt, stats)
     device = model._xyz.device
     ns, nd = model.num_static, model.num_dynamic
     max_dur = model.duration if max_dur is None else max(float(max_dur), model.interval)
@@ -131,14 +162,16 @@ def extract_dynamic_points(model, stats, opt, viewpoint_loc, timestamp, vis_filt
         vis_filter = vis_filter.view(torch.uint8)
     if not vis_filter.is_cuda or vis_filter.dtype != torch.uint8 or not vis_filter.is_contiguous() or tuple(vis_filter.shape) != (ns,):
         raise RuntimeError("extract_dynamic_points: vis_filter must be a contiguous bool / uint8 [Ns] tensor on the device")
-    cam = torch.as_tensor(viewpoint_loc, dtype=torch.float32).reshape(3).to(device).contiguous()
+    cam = _broadcast(torch.as_tensor(viewpoint_loc, dtype=torch.float32).reshape(3).to(device).contiguous(), stats, src)
+    vis_filter = _broadcast(vis_filter.clone(), stats, src) if getattr(stats, "shared", False) else vis_filter
     zero = {"static": dict(zip(COUNT_NAMES, [ns] + [0] * 6 + [ns])), "dynamic": dict(zip(COUNT_NAMES, [nd] + [0] * 6 + [nd])),
             "threshold": float("nan"), "visible": 0}
     if ns == 0:
         return zero
     mp, counts, selected, counts_out, result = _classify(model, stats, cam, vis_filter, _f32(percentile), _f32(motion_thres * extent),
                                                          _f32(min_motion_thres * extent))
-    back = torch.cat([counts_out, result.view(torch.int32)]).cpu()                    # the one read-back
+    back = torch.tensor(_same_on_every_rank(torch.cat([counts_out, result.view(torch.int32)]), stats, "extract_dynamic_points"),
+                        dtype=torch.int32)                                                 # the one read-back
     n_new, keep = int(back[0]), int(back[1])
     theta, visible = float(back[2:3].view(torch.float32)), int(back[2 + SELECT_COUNT])
     if visible == 0:
@@ -203,7 +236,7 @@ def extract_dynamic_points(model, stats, opt, viewpoint_loc, timestamp, vis_filt
     group.split_div = 1.6
     _apply(descs_s, [group, Ex4dDensifyApplyGroup()], device)
     _rebind(model, opt, new_params, new_moments)
-    stats.static, stats.dynamic = block_s, block_d
+    stats._resized(block_s, block_d)
     return out
 
 

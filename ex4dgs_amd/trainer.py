@@ -113,7 +113,6 @@ class FrameTrainer:
         lrs = dict(reference_lrs(spatial_lr_scale), **(lrs or {}))
         self.lrs = [lrs[n] for n in self.names]
         self.opt = None
-        self.exchange = None
         # one gradient window per rank reaches ex4d_radam_step_sliced: more ranks than it takes windows -> dense keyframe gradients
         from .optim import MAX_WINDOWS
         gather_world = self.world if self.mode in ("allreduce", "sharded") else 1      # exchange "none": nothing is summed over ranks, keyframes included
@@ -133,19 +132,11 @@ class FrameTrainer:
         # attribute backward still runs; the other parameters follow it
         self.feat_pos = [i for i in self.feature_idx]
         self.rest_pos = [i for i in range(len(self.params)) if i not in self.kf_idx and i not in self.feature_idx]
-        self.exchange_feat = None
-        if self.mode == "sharded":
-            self.opt = xdist.ShardedRAdam(self.params, self.lrs, group=group, nan_to_num=[n in NAN_TO_NUM for n in self.names], force=force,
-                                          sliced={i: self.sliced_shapes[self.names[i]][0] for i in self.kf_idx})
-            self.exchange = self.opt.exchange
-        else:
-            if self.mode == "allreduce":
-                self.exchange_feat = xdist.ParamGradExchange([self.params[i].shape for i in self.feat_pos], self.device, mode="allreduce", group=group, force=force)
-                self.exchange = xdist.ParamGradExchange([self.params[i].shape for i in self.rest_pos], self.device, mode="allreduce", group=group, force=force)
-            if optimizer:
-                self.m = [torch.zeros_like(p) for p in self.params]
-                self.v = [torch.zeros_like(p) for p in self.params]
-                self.steps = 0
+        self._make_exchanges()
+        if self.mode != "sharded" and optimizer:
+            self.m = [torch.zeros_like(p) for p in self.params]
+            self.v = [torch.zeros_like(p) for p in self.params]
+            self.steps = 0
         self.optimizer = bool(optimizer) or self.mode == "sharded"
         # (round 5 made the non-blocking forward the default wherever the class can recover from an overflow by itself; round 6 measured the
         # synchronous forward -- its read-back off the caller's stream now -- equal or faster, and it needs no capacity policy: opt-in again)
@@ -173,6 +164,22 @@ class FrameTrainer:
             self.pgrad[i] = torch.zeros(shape, dtype=torch.float32, device=self.device)
             if self.mode != "sharded":      # replicated optimizer: every rank needs every window (all-gather); sharded: row all-to-all inside ShardedRAdam
                 self.kf_gather.append(xdist.SliceGather(shape, self.device, group=self._group, local_only=(self.mode != "allreduce"), force=self._force))
+
+    def _make_exchanges(self):
+        """The collectives sized by the parameters: the two gradient exchanges of the replicated modes, or the sharded optimizer with
+        its reduce-scatter (a rebuilt one takes over the step counts; its moments are loaded by the caller)."""
+        self.exchange_feat = self.exchange = None
+        if self.mode == "sharded":
+            old = self.opt
+            self.opt = xdist.ShardedRAdam(self.params, self.lrs, group=self._group, nan_to_num=[n in NAN_TO_NUM for n in self.names], force=self._force,
+                                          sliced={i: self.sliced_shapes[self.names[i]][0] for i in self.kf_idx})
+            if old is not None:
+                self.opt.steps = list(old.steps)
+            self.exchange = self.opt.exchange
+        elif self.mode == "allreduce":
+            shapes = lambda pos: [self.params[i].shape for i in pos]
+            self.exchange_feat = xdist.ParamGradExchange(shapes(self.feat_pos), self.device, mode="allreduce", group=self._group, force=self._force)
+            self.exchange = xdist.ParamGradExchange(shapes(self.rest_pos), self.device, mode="allreduce", group=self._group, force=self._force)
 
     def _settings(self, cam, bg, near, far):
         H, W = int(cam.image_height), int(cam.image_width)
@@ -399,23 +406,28 @@ class FrameTrainer:
     def begin_density_control(self):
         """Before densify_and_prune / a prune (ex4dgs_amd.densify) replaces the model's tensors: settles a pending asynchronous frame and
         DROPS the pending gradients without applying them -- train.py densifies before optimizer.step(), which then skips every replaced
-        parameter (no .grad): that iteration's update is lost and the step count does not advance."""
-        if self.mode != "none" or self.k != 1:
-            raise NotImplementedError("density control on a FrameTrainer needs exchange='none' and views_per_step=1: "
-                                      "multi-rank density control needs a reduction of the statistics first")
+        parameter (no .grad): that iteration's update is lost and the step count does not advance.  With an exchange ("allreduce",
+        "sharded") the pending collectives are waited for first; every rank makes the density-control call at the same iteration, with
+        densify.DensityStats(model, shared=True)."""
+        if self.k != 1:
+            raise NotImplementedError("density control on a FrameTrainer needs views_per_step=1 (the accumulated gradients of a group of views "
+                                      "would be dropped half way)")
         self._drain()
         self._grads = None
 
     def rebind_parameters(self, moments=None):
         """After the model's tensors were replaced (ex4dgs_amd.densify): picks up the new parameters and rebuilds the P-sized buffers
-        (gradient buffers, keyframe slice gathers).  moments: {name: (exp_avg, exp_avg_sq)} remapped to the new rows (None: zeros)."""
+        (gradient buffers, keyframe slice gathers, gradient exchanges, the sharded optimizer with its step counts).  moments: {name: (exp_avg, exp_avg_sq)} remapped to the new rows (None: zeros)."""
         if self._grads is not None:
             raise RuntimeError("rebind_parameters: pending gradients (call begin_density_control first)")
         self.params = [getattr(self.model, n) for n in self.names]
         self._make_grad_buffers()
-        if self.optimizer:
-            moments = moments or {}
-            pairs = [moments.get(n) for n in self.names]
+        self._make_exchanges()
+        moments = moments or {}
+        pairs = [moments.get(n) for n in self.names]
+        if self.mode == "sharded":
+            self.opt.load_moments(pairs)
+        elif self.optimizer:
             self.m = [pr[0] if pr is not None else torch.zeros_like(p) for pr, p in zip(pairs, self.params)]
             self.v = [pr[1] if pr is not None else torch.zeros_like(p) for pr, p in zip(pairs, self.params)]
 

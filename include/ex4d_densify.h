@@ -44,6 +44,23 @@ enum {
 int ex4d_densify_stats(float *stats_s, int64_t ns, float *stats_d, int64_t nd, const int32_t *radii, const float *vgrad,
                        const float *egrad, float timestamp, int32_t flags, void *stream);
 
+/* ---- merge of the ranks' statistics (multi-rank training): every rank accumulates ex4d_densify_stats into a PENDING block that
+ * starts at the initial values above, the pending blocks are all-gathered, and this call folds them into the running TOTAL of one
+ * group -- a left fold in rank order, rank 0 first, so every rank computes the same bits.  total [9, n] (read and written); pending
+ * [world, 9, n] contiguous, block w from rank w; own_pending [9, n] or NULL: the caller's own pending block, reset to the initial
+ * values by the same launch.  Per element, with t of the total and d of a rank:
+ *     GRAD_ACCUM, DENOM, ERROR_ACCUM, SSIM_ACCUM, ERROR_DENOM    t = t + d                  (float32 add)
+ *     MAX_RADII                                                  t = d > t ? d : t
+ *     MIN_RADII                                                  t = d < t ? d : t
+ *     ERROR_MIN / ERROR_MIN_T                                    if (t_min > d_min) { t_ts = d_ts; t_min = d_min; }
+ * The last comparison is the strict one of ex4d_densify_stats: on a tie the lower rank keeps its timestamp, a NaN minimum is never
+ * taken and a NaN total never replaced.  A pending block at the initial values leaves the total unchanged bit for bit (a sum row
+ * holding -0.0 excepted: -0.0 + 0 is +0.0; sums that start at +0 never reach -0.0).  world == 0 or n == 0: valid, nothing is done
+ * (own_pending is not written).  Refused before any HIP call, with "densify_stats_merge: negative rank count or size", "...: null or
+ * misaligned block" (float alignment is all that is asked) or "...: the total, the pending blocks and the own block must not overlap".
+ * One launch, no atomics, no host synchronisation (graph-capturable). */
+int ex4d_densify_stats_merge(float *total, const float *pending, int32_t world, int64_t n, float *own_pending, void *stream);
+
 /* ---- the gate of prune_nan_points (:1230, :1234: isnan().any() per group) without a read-back: flags2[0] = any(isnan(a[0 .. n_a))),
  * flags2[1] likewise for b; either array may be empty (n = 0, pointer then unused, may be NULL).  a and b need only float alignment.
  * flags2 (device int32[2]) is fully written: cleared by a kernel of the library, then one launch streams both arrays.  No atomics, no
