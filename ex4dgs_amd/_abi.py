@@ -218,7 +218,8 @@ PROTOTYPES = {
         _value("ex4d_reg_last_error", text),
         _value("ex4d_reg_scratch_bytes", size),
         _status("ex4d_reg_forward", vp, i64, vp, vp, i64, i32, f64, f64, f64, vp, vp, vp),
-        _status("ex4d_reg_backward", vp, vp, i64, vp, vp, vp, vp, i64, i32, f64, f64, f64, vp, i32, vp))),
+        _status("ex4d_reg_backward", vp, vp, i64, vp, vp, vp, vp, i64, i32, f64, f64, f64, vp, i32, vp),
+        _status("ex4d_reg_backward_range", i32, vp, i64, i32, i64, i64, vp, f64, i32, vp))),
     "ex4d_trainer.h": ("ex4d_trainer_last_error", (                  # Ex4dTrainer * is opaque: c_void_p
         _value("ex4d_trainer_last_error", text),
         _value("ex4d_trainer_create", vp, P(Ex4dTrainerConfig), P(vp)),

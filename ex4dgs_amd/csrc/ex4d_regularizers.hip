@@ -1,6 +1,7 @@
 // The motion regularisers of train.py:155-168 as a stand-alone op (include/ex4d_regularizers.h): loss value and dense gradients.
 // The per-iteration hot path is the regularised sliced RAdam step (ex4d_optim.hip), which never materialises these gradients; this
-// file serves autograd users, the dense-gradient trainer paths, the _xyz_disp term and the reported loss value.
+// file serves autograd users, the dense-gradient trainer paths (whole tensors, or the element range a rank of the sharded optimizer
+// owns: ex4d_reg_backward_range), the _xyz_disp term and the reported loss value.
 // ffp-contract is off for this file: the gradient arithmetic (ex4d_reg_rows.h) is shared bit for bit with ex4d_optim.hip.
 #include "ex4d_internal.h"
 #include "ex4d_reg_rows.h"
@@ -80,32 +81,60 @@ __global__ __launch_bounds__(REG_THREADS) void reg_finish_kernel(const double *p
 
 __device__ __forceinline__ float scaled(float coef, const float *upstream) { return upstream ? coef * upstream[0] : coef; }
 
-__global__ __launch_bounds__(REG_THREADS) void reg_bwd_static_kernel(const float *disp, float *g, long long Ns, float coef, const float *upstream, int accumulate)
+// kinds of ex4d_reg_backward_range: ex4d_reg::KIND_MOTION (1, [rows,K,3]) and KIND_ROT (2, [rows,K,4]) keep reg_kind's numbering; 3 is static_reg
+constexpr int KIND_STATIC = 3;   // [rows,3]: one slice per row, K plays no part
+template <int KIND> constexpr int kind_width = KIND == ex4d_reg::KIND_ROT ? 4 : 3;
+
+// gradient of slice s of the tensor: row s of [rows,3], or keyframe s % K of row s / K (the whole row is read where the term needs it)
+template <int KIND>
+__device__ __forceinline__ void slice_grad(const float *p, int K, long long s, float c, float (&r)[kind_width<KIND>])
 {
-    const long long i = (long long)blockIdx.x * REG_THREADS + threadIdx.x;
-    if (i >= Ns) return;
-    float r[3];
-    ex4d_reg::static_grad(disp + 3 * i, scaled(coef, upstream), r);
-#pragma unroll
-    for (int j = 0; j < 3; j++) g[3 * i + j] = accumulate ? g[3 * i + j] + r[j] : r[j];
+    if constexpr (KIND == KIND_STATIC) ex4d_reg::static_grad(p + 3 * s, c, r);
+    else {
+        const long long row = s / K;
+        const int k = (int)(s - row * K);
+        if constexpr (KIND == ex4d_reg::KIND_MOTION) ex4d_reg::motion_grad(p + row * K * 3, K, k, c, r);
+        else ex4d_reg::rot_grad(p + row * K * 4, K, k, c, r);
+    }
 }
 
-// one thread per (row, keyframe) slice; kind: ex4d_reg::KIND_MOTION ([Nd,K,3]) or KIND_ROT ([Nd,K,4])
+// one thread per slice: a row of _xyz_disp (KIND_STATIC, K = 1) or a (row, keyframe) of a keyframe tensor
 template <int KIND>
-__global__ __launch_bounds__(REG_THREADS) void reg_bwd_keyframe_kernel(const float *p, float *g, long long Nd, int K, float coef, const float *upstream,
-                                                                       int accumulate)
+__global__ __launch_bounds__(REG_THREADS) void reg_bwd_kernel(const float *p, float *g, long long slices, int K, float coef, const float *upstream, int accumulate)
 {
-    constexpr int C = KIND == ex4d_reg::KIND_MOTION ? 3 : 4;
+    constexpr int C = kind_width<KIND>;
     const long long s = (long long)blockIdx.x * REG_THREADS + threadIdx.x;
-    if (s >= Nd * K) return;
-    const long long row = s / K;
-    const int k = (int)(s - row * K);
+    if (s >= slices) return;
     float r[C];
-    const float c = scaled(coef, upstream);
-    if constexpr (KIND == ex4d_reg::KIND_MOTION) ex4d_reg::motion_grad(p + row * K * C, K, k, c, r);
-    else ex4d_reg::rot_grad(p + row * K * C, K, k, c, r);
+    slice_grad<KIND>(p, K, s, scaled(coef, upstream), r);
 #pragma unroll
     for (int j = 0; j < C; j++) g[s * C + j] = accumulate ? g[s * C + j] + r[j] : r[j];
+}
+
+// the same over the slices s0 .. s0 + slices - 1 that overlap the flat element range [lo, hi): g[0] belongs to element lo, and of a
+// slice the range cuts only the elements inside it are written
+template <int KIND>
+__global__ __launch_bounds__(REG_THREADS) void reg_bwd_range_kernel(const float *p, float *g, long long s0, long long slices, int K, long long lo, long long hi,
+                                                                    float coef, int accumulate)
+{
+    constexpr int C = kind_width<KIND>;
+    const long long i = (long long)blockIdx.x * REG_THREADS + threadIdx.x;
+    if (i >= slices) return;
+    const long long s = s0 + i;
+    float r[C];
+    slice_grad<KIND>(p, K, s, coef, r);
+    const long long e0 = s * C;
+    if (e0 >= lo && e0 + C <= hi) {      // a whole slice (all but the range's two ends): the dense kernel's stores, no test per element
+        float *o = g + (e0 - lo);
+#pragma unroll
+        for (int j = 0; j < C; j++) o[j] = accumulate ? o[j] + r[j] : r[j];
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < C; j++) {
+        const long long e = e0 + j;
+        if (e >= lo && e < hi) g[e - lo] = accumulate ? g[e - lo] + r[j] : r[j];
+    }
 }
 
 thread_local char g_reg_err[256] = "";
@@ -161,13 +190,64 @@ int ex4d_reg_backward(const float *xyz_disp, float *g_xyz_disp, int64_t Ns, cons
     const double pairs = (double)Nd * (K - 1);
     const float cm = pairs > 0 ? (float)(motion_reg / pairs) : 0.f, cr = pairs > 0 ? (float)(rot_reg / pairs) : 0.f;
     if (g_xyz_disp && Ns > 0 && !(accumulate && cs == 0.f))
-        hipLaunchKernelGGL(reg_bwd_static_kernel, dim3(blocks_for(Ns)), dim3(REG_THREADS), 0, stream, xyz_disp, g_xyz_disp, (long long)Ns, cs, upstream, (int)accumulate);
+        hipLaunchKernelGGL(reg_bwd_kernel<KIND_STATIC>, dim3(blocks_for(Ns)), dim3(REG_THREADS), 0, stream, xyz_disp, g_xyz_disp, (long long)Ns, 1, cs, upstream,
+                           (int)accumulate);
     if (g_xyz_motion && Nd > 0 && !(accumulate && cm == 0.f))
-        hipLaunchKernelGGL(reg_bwd_keyframe_kernel<ex4d_reg::KIND_MOTION>, dim3(blocks_for(Nd * K)), dim3(REG_THREADS), 0, stream, xyz_motion, g_xyz_motion,
-                           (long long)Nd, (int)K, cm, upstream, (int)accumulate);
+        hipLaunchKernelGGL(reg_bwd_kernel<ex4d_reg::KIND_MOTION>, dim3(blocks_for(Nd * K)), dim3(REG_THREADS), 0, stream, xyz_motion, g_xyz_motion,
+                           (long long)Nd * K, (int)K, cm, upstream, (int)accumulate);
     if (g_rotation_motion && Nd > 0 && !(accumulate && cr == 0.f))
-        hipLaunchKernelGGL(reg_bwd_keyframe_kernel<ex4d_reg::KIND_ROT>, dim3(blocks_for(Nd * K)), dim3(REG_THREADS), 0, stream, rotation_motion, g_rotation_motion,
-                           (long long)Nd, (int)K, cr, upstream, (int)accumulate);
+        hipLaunchKernelGGL(reg_bwd_kernel<ex4d_reg::KIND_ROT>, dim3(blocks_for(Nd * K)), dim3(REG_THREADS), 0, stream, rotation_motion, g_rotation_motion,
+                           (long long)Nd * K, (int)K, cr, upstream, (int)accumulate);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { snprintf(g_reg_err, sizeof(g_reg_err), "launch failed: %s", hipGetErrorString(e)); return EX4D_ERR_HIP; }
+    return EX4D_OK;
+}
+
+int ex4d_reg_backward_range(int32_t kind, const float *param, int64_t rows, int32_t K, int64_t lo, int64_t hi, float *grad, double weight,
+                            int32_t accumulate, void *stream_)
+{
+    g_reg_err[0] = 0;
+    if (kind != ex4d_reg::KIND_MOTION && kind != ex4d_reg::KIND_ROT && kind != KIND_STATIC) {
+        snprintf(g_reg_err, sizeof(g_reg_err), "ex4d_reg_backward_range: unknown kind %d (1 motion_reg, 2 rot_reg, 3 static_reg)", (int)kind);
+        return EX4D_ERR_ARG;
+    }
+    if (kind == KIND_STATIC) K = 1;
+    const int C = kind == ex4d_reg::KIND_ROT ? 4 : 3;
+    if (rows < 0 || (rows > 0 && (K < 1 || rows > INT64_MAX / ((int64_t)K * C)))) {
+        snprintf(g_reg_err, sizeof(g_reg_err), "ex4d_reg_backward_range: negative or overflowing size, or K < 1");
+        return EX4D_ERR_ARG;
+    }
+    const int64_t numel = rows > 0 ? rows * K * C : 0;
+    if (lo < 0 || hi > numel || lo > hi) {
+        snprintf(g_reg_err, sizeof(g_reg_err), "ex4d_reg_backward_range: element range [%lld, %lld) is not inside the tensor's [0, %lld)", (long long)lo,
+                 (long long)hi, (long long)numel);
+        return EX4D_ERR_ARG;
+    }
+    if (lo == hi) return EX4D_OK;
+    if (!param || !grad) {
+        snprintf(g_reg_err, sizeof(g_reg_err), "ex4d_reg_backward_range: null parameter or gradient");
+        return EX4D_ERR_ARG;
+    }
+    // the coefficient of ex4d_reg_backward: 0 where the term is off or has nothing to average (accumulate: nothing to add)
+    const double count = kind == KIND_STATIC ? (double)rows : (double)rows * (K - 1);
+    const float coef = count > 0 ? (float)(weight / count) : 0.f;
+    if (accumulate && coef == 0.f) return EX4D_OK;
+    const int64_t s0 = lo / C, slices = (hi - 1) / C - s0 + 1;          // the slices the range overlaps, cut ones included
+    if ((slices + REG_THREADS) / REG_THREADS > 0x7fffffffLL) {
+        snprintf(g_reg_err, sizeof(g_reg_err), "ex4d_reg_backward_range: too many elements for one launch");
+        return EX4D_ERR_ARG;
+    }
+    hipStream_t stream = (hipStream_t)stream_;
+    const dim3 grid(blocks_for(slices)), block(REG_THREADS);
+    if (kind == KIND_STATIC)
+        hipLaunchKernelGGL(reg_bwd_range_kernel<KIND_STATIC>, grid, block, 0, stream, param, grad, (long long)s0, (long long)slices, 1, (long long)lo, (long long)hi,
+                           coef, (int)accumulate);
+    else if (kind == ex4d_reg::KIND_MOTION)
+        hipLaunchKernelGGL(reg_bwd_range_kernel<ex4d_reg::KIND_MOTION>, grid, block, 0, stream, param, grad, (long long)s0, (long long)slices, (int)K,
+                           (long long)lo, (long long)hi, coef, (int)accumulate);
+    else
+        hipLaunchKernelGGL(reg_bwd_range_kernel<ex4d_reg::KIND_ROT>, grid, block, 0, stream, param, grad, (long long)s0, (long long)slices, (int)K,
+                           (long long)lo, (long long)hi, coef, (int)accumulate);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { snprintf(g_reg_err, sizeof(g_reg_err), "launch failed: %s", hipGetErrorString(e)); return EX4D_ERR_HIP; }
     return EX4D_OK;

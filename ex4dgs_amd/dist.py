@@ -407,17 +407,24 @@ class ShardedRAdam:
     1/W of the optimizer's 28 B/element HBM traffic per rank; the same bytes per link as the all-reduce it replaces.
 
     params: list of contiguous float32 tensors (updated in place); lrs: per-tensor learning rates.
-    step_fn(items, betas, eps, device): defaults to the fused HIP launch (optim.radam_step_raw); the CPU tests inject the oracle."""
+    step_fn(items, betas, eps, device): defaults to the fused HIP launch (optim.radam_step_raw); the CPU tests inject the oracle.
+
+    Motion regularisers (step(reg=...)): the term is added once per step, last, to the gradient summed over the ranks -- by the owner of
+    each element, after the exchange, never before it.  Every rank therefore ends a step with the bits of a single-process step fed the
+    same reduced gradient.  The weights must be the same on every rank (regularizers.regularizer_weights makes them so); nothing checks it."""
 
     def __init__(self, params, lrs, betas=(0.9, 0.999), eps=1e-8, group=None, step_fn=None, small_bytes=1 << 20, nan_to_num=None, force=False,
-                 sliced=None, sliced_step_fn=None):
+                 sliced=None, sliced_step_fn=None, sliced_reg_step_fn=None, reg_range_fn=None):
         """nan_to_num: per-tensor flags -- the gradient of a flagged tensor is read through torch.nan_to_num like the replicated
         paths do for _opacity_duration_var (train.py:244-247; ADVICE r03: without it one non-finite gradient poisons the sharded
         parameter and its moments for good, and "bit-identical to the replicated update" stops holding).
         sliced: {tensor index: count} for keyframe tensors [rows, K, C] whose gradient arrives as a [rows, count, C] WINDOW plus its
         first keyframe (launch_exchange(..., windows=...)): sharded by whole rows, exchanged by SliceRowExchange, updated by
         ex4d_radam_step_sliced on the owned rows (sliced_step_fn: defaults to optim.radam_step_sliced_raw; the CPU tests inject an
-        oracle).  At most optim.MAX_WINDOWS ranks (one window per rank reaches the kernel)."""
+        oracle).  At most optim.MAX_WINDOWS ranks (one window per rank reaches the kernel).
+        sliced_reg_step_fn(items, betas, eps, device): the sliced step of a regularised step (defaults to
+        optim.radam_step_sliced_reg_raw); reg_range_fn(kind, param, lo, hi, grad, weight): adds one term's gradient over the element
+        range [lo, hi) of `param` to `grad` (hi - lo elements; defaults to regularizers.backward_range_raw).  The CPU tests inject oracles."""
         self.params = list(params)
         self.sliced = {int(i): int(c) for i, c in (sliced or {}).items()}
         self.lrs = [float(x) for x in lrs]
@@ -442,6 +449,14 @@ class ShardedRAdam:
                 raise ValueError(f"sliced keyframe gradients take one window per rank, at most {MAX_WINDOWS} (use dense keyframe gradients beyond)")
             sliced_step_fn = radam_step_sliced_raw
         self.sliced_step_fn = sliced_step_fn
+        if self.sliced and sliced_reg_step_fn is None:
+            from .optim import radam_step_sliced_reg_raw
+            sliced_reg_step_fn = radam_step_sliced_reg_raw
+        self.sliced_reg_step_fn = sliced_reg_step_fn
+        if reg_range_fn is None:
+            from .regularizers import backward_range_raw
+            reg_range_fn = backward_range_raw
+        self.reg_range_fn = reg_range_fn
         self.steps = [0] * len(self.params)
         # per tensor: is it small (updated redundantly by every rank from the all-reduced flat message) and its shard granule
         self.small = [False] * len(self.params)
@@ -516,12 +531,20 @@ class ShardedRAdam:
             w, first = windows[i]
             ex.launch(w, first)
 
-    def step(self, grads=None, windows=None):
+    def step(self, grads=None, windows=None, reg=None):
+        """reg: {tensor index: (kind, weight, reg_rows)} -- the motion regulariser of this step on that tensor (kinds and weights of
+        regularizers.backward_range_raw; reg_rows: the tensor's full row count, the one of the term's mean).  A sliced tensor's owned rows
+        go through the regularised sliced step (windows in rank order, the term last); a dense tensor's term is added to the reduced
+        gradient of the owned element range before the step -- a small tensor is reduced whole and updated by every rank, which adds the
+        whole term.  None, or all weights 0: the calls of a step without regularisers."""
         if grads is not None:
             self.launch_exchange(grads, windows)
         self.exchange.wait()
         for ex in self.row_exchange.values():
             ex.wait()
+        reg = {int(i): (int(kind), float(weight), int(rows)) for i, (kind, weight, rows) in (reg or {}).items()}
+        if not any(weight != 0.0 for _, weight, _ in reg.values()):
+            reg = {}
         ptr = lambda x: x.data_ptr() if x.is_cuda else x       # the CPU tests' injected step functions take the tensors themselves
         items, sliced_items = [], []
         for i, (p, g) in enumerate(zip(self.params, self._grads)):
@@ -538,15 +561,22 @@ class ShardedRAdam:
                     if not cuda:                # CPU tests: the positions are host-readable
                         firsts = ex.first.tolist()
                         wins = [(int(firsts[r]) if f is None else f, c, t) for r, (f, c, t) in enumerate(wins)]
-                    sliced_items.append((ptr(pv), ptr(self.exp_avg[i]), ptr(self.exp_avg_sq[i]), rows, K, Cc, self.lrs[i], self.steps[i], wins,
-                                         (ex.first.data_ptr() if (cuda and ex.active()) else None)))
+                    item = (ptr(pv), ptr(self.exp_avg[i]), ptr(self.exp_avg_sq[i]), rows, K, Cc, self.lrs[i], self.steps[i], wins,
+                            (ex.first.data_ptr() if (cuda and ex.active()) else None))
+                    if reg:                     # one launch for the step's sliced tensors: those without a term carry kind 0
+                        item += reg.get(i, (0, 0.0, rows_total))
+                    sliced_items.append(item)
                 continue
             if hi > lo:
                 pv, gv = p.view(-1)[lo:hi], g.view(-1)[lo:hi]
+                if i in reg and reg[i][1] != 0.0:
+                    kind, weight, reg_rows = reg[i]
+                    assert reg_rows == p.shape[0], (i, reg_rows, tuple(p.shape))
+                    self.reg_range_fn(kind, p.detach(), lo, hi, gv, weight)      # after the exchange: gv holds the sum over the ranks
                 items.append((ptr(pv), ptr(gv), ptr(self.exp_avg[i]), ptr(self.exp_avg_sq[i]), hi - lo, self.lrs[i], self.steps[i], self.nan_to_num[i]))
         self.step_fn(items, self.betas, self.eps, self.device)
         if sliced_items:
-            self.sliced_step_fn(sliced_items, self.betas, self.eps, self.device)
+            (self.sliced_reg_step_fn if reg else self.sliced_step_fn)(sliced_items, self.betas, self.eps, self.device)
         if self.device.type == "cuda":
             torch.autograd.graph.increment_version(self.params)        # written through raw pointers
         if self.world > 1 or self.force:

@@ -6,7 +6,9 @@
 replaces the three `if opt.*_reg > 0 ...` blocks: one forward launch pair and one backward launch per tensor instead of ~20
 element-wise torch kernels and their autograd graph over the keyframe tensors.  Works with torch.optim.RAdam and FusedRAdam.
 trainer.FrameTrainer(regularizers=...) goes further: with sliced keyframe gradients the two keyframe terms are formed inside the
-optimizer step (optim.radam_step_sliced_reg_raw) and their dense gradient never exists.
+optimizer step (optim.radam_step_sliced_reg_raw) and their dense gradient never exists.  On several ranks the term is added once per
+optimizer step, last, to the gradient summed over ranks and views; backward_range_raw is the gradient of one term
+over the element range a rank of the sharded optimizer owns.
 No CPU fallback: everything here needs the HIP library and a ROCm device.
 """
 import torch
@@ -21,12 +23,16 @@ def _get(opt, name):
     return opt[name] if isinstance(opt, dict) else getattr(opt, name)
 
 
-def regularizer_weights(opt, iteration, num_dynamic):
+def regularizer_weights(opt, iteration, num_dynamic, views=1):
     """The gates of train.py:156, :159, :163: (static_reg, motion_reg, rot_reg) as they act at `iteration` (0.0 = term off).
-    opt: the reference's OptimizationParams (or a dict of its fields)."""
+    opt: the reference's OptimizationParams (or a dict of its fields).
+    views: multiplies the three weights.  A FrameTrainer adds the term once per optimizer step, to the gradient summed over N ranks x k
+    views, where the reference adds one term per view: views = N * k restores the reference's balance of data and regulariser.
+    The result depends on replicated values only (num_dynamic is the same on every rank), so every rank gets the same weights -- which
+    multi-rank training requires and does not check."""
     late_static = iteration > _get(opt, "progressive_growing_steps") + _get(opt, "make_dynamic_interval")
     late_motion = iteration > _get(opt, "progressive_growing_steps") * _get(opt, "extract_every") + _get(opt, "make_dynamic_interval")
-    s, m, r = (float(_get(opt, n)) for n in ("static_reg", "motion_reg", "rot_reg"))
+    s, m, r = (float(_get(opt, n)) * views for n in ("static_reg", "motion_reg", "rot_reg"))
     return (s if s > 0 and late_static else 0.0,
             m if m > 0 and late_motion and num_dynamic > 0 else 0.0,
             r if r > 0 and late_motion and num_dynamic > 0 else 0.0)
@@ -87,6 +93,26 @@ def backward_raw(xyz_disp, xyz_motion, rotation_motion, weights, grads, upstream
     with _abi.stream(dev) as stream:
         _abi.call("ex4d_reg_backward", ptr(xyz_disp), ptr(grads[0]), Ns, ptr(xyz_motion), ptr(grads[1]), ptr(rotation_motion), ptr(grads[2]), Nd, K,
                   float(weights[0]), float(weights[1]), float(weights[2]), ptr(upstream), int(bool(accumulate)), stream)
+
+
+REG_MOTION, REG_ROT, REG_STATIC = 1, 2, 3      # kinds of backward_range_raw (1 and 2: optim.REG_MOTION / REG_ROT)
+
+
+def backward_range_raw(kind, param, lo, hi, grad, weight, accumulate=True):
+    """ex4d_reg_backward_range on the current stream: one term's gradient over the flat element range [lo, hi) of `param`, the bits
+    backward_raw gives those elements.  kind: REG_MOTION (param [rows,K,3]), REG_ROT ([rows,K,4]) or REG_STATIC ([rows,3]); param: the
+    WHOLE tensor (the mean counts its rows); grad: contiguous float32 of hi - lo elements on param's device, grad[0] belongs to element
+    lo (e.g. a view of a rank's gradient shard); accumulate: add (the default: the term joins a summed gradient) instead of write."""
+    d, m, r = (param if kind == k else None for k in (REG_STATIC, REG_MOTION, REG_ROT))
+    if d is None and m is None and r is None:
+        raise RuntimeError(f"regularizers: unknown kind {kind} (REG_MOTION, REG_ROT, REG_STATIC)")
+    dev, Ns, Nd, K = _check_inputs(d, m, r)
+    lo, hi = int(lo), int(hi)                      # (a range outside the tensor is refused by the library, with its text)
+    if grad is None or grad.dtype != torch.float32 or not grad.is_contiguous() or grad.device != param.device or grad.numel() != max(hi - lo, 0):
+        raise RuntimeError("regularizers: the gradient must be contiguous float32 of hi - lo elements, on its parameter's device")
+    with _abi.stream(dev) as stream:
+        _abi.call("ex4d_reg_backward_range", int(kind), ptr(param), Ns if kind == REG_STATIC else Nd, K, lo, hi, ptr(grad), float(weight),
+                  int(bool(accumulate)), stream)
 
 
 class _MotionRegularizers(torch.autograd.Function):

@@ -72,7 +72,14 @@ class FrameTrainer:
         lambda: regularizers.regularizer_weights(opt, iteration, Nd).  Their gradients join the frame's in the optimizer step: with sliced
         keyframe gradients the two keyframe terms are formed inside ex4d_radam_step_sliced_reg from the rows it updates (no dense
         gradient), _xyz_disp's term is added to its gradient buffer; with dense keyframe gradients all three are added once per optimizer
-        step.  last["reg"]: float32[4] on the device = (static, motion, rot mean, weighted sum) at the frame's parameters."""
+        step.  last["reg"]: float32[4] on the device = (static, motion, rot mean, weighted sum) at the frame's parameters.
+        With an exchange the terms are added once per optimizer step, last, to the gradient summed over ranks and views -- after the
+        exchange, never before it: "allreduce" adds them to the reduced buffers / forms them in the fused step over the gathered windows,
+        "sharded" hands them to ShardedRAdam.step(reg=...), whose owners add them to their element ranges or rows.  Every rank ends a step
+        with the bits of a single-process step fed the reduced gradient.  The weights must be equal on all ranks (nothing checks it;
+        regularizer_weights depends on replicated values only), and regularizer_weights(..., views=N k) restores the reference's one term
+        per view.  exchange="allreduce" without a process group of several ranks (and without force_collectives) would train with no
+        exchange at all: with regularizers that request is still refused (NotImplementedError); ask for exchange="none"."""
         assert exchange in ("none", "allreduce", "sharded")
         self.k = int(views_per_step)
         assert self.k >= 1
@@ -87,8 +94,6 @@ class FrameTrainer:
         self.regularizers = regularizers
         self._reg_w = self._reg_out = self._reg_scratch = None
         if regularizers is not None:
-            if exchange != "none":
-                raise NotImplementedError("regularizers on a FrameTrainer need exchange='none': every rank would add the full term to its gradient")
             if not optimizer:
                 raise ValueError("regularizers join the gradients inside the optimizer step: optimizer=True")
             if model.num_dynamic > 0 and self.k == 1:
@@ -106,6 +111,11 @@ class FrameTrainer:
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         force = xdist._forced(force_collectives) and dist.is_initialized()
         self.mode = exchange if (self.world > 1 or exchange == "sharded" or force) else "none"
+        if regularizers is not None and self.mode != exchange:
+            # the part of the former refusal that stays: an exchange was asked for and none takes place (no process group of several
+            # ranks, no force_collectives), so weights scaled for N ranks (regularizer_weights(views=)) would act on one rank's gradient
+            raise NotImplementedError(f"regularizers on a FrameTrainer with exchange='{exchange}' need a process group of several ranks "
+                                      "(or force_collectives): no exchange would take place; ask for exchange='none'")
         self.overlap = overlap
         self.side = torch.cuda.Stream(device=self.device) if overlap else None
         self._group, self._force = group, force
@@ -308,35 +318,42 @@ class FrameTrainer:
                 if self.mode == "sharded":                   # row all-to-all of the windows (inside the sharded optimizer)
                     windows = {i: (gout[i], first) for i, first in zip(self.kf_idx, (hint[0], hint[2]))}
             grads = [fgrads[self.feature_idx.index(i)] if i in self.feature_idx else gout[i] for i in range(len(self.params))]
-            if self.k > 1:
-                # views 1 .. k-1 of the group: added to the accumulators, nothing goes on the wire, no optimizer step follows
-                if self._acc is None:
-                    self._acc = [torch.zeros_like(p) for p in self.params]
-                if self._nacc == 0:
-                    if self.exchange_feat is not None:
-                        self.exchange_feat.wait()            # (the previous group's collectives own the accumulators until here)
-                    for a, g_ in zip(self._acc, grads):
-                        a.copy_(g_)
-                else:
-                    torch._foreach_add_(self._acc, list(grads))
-                self._nacc += 1
-                if self._nacc < self.k:
-                    self._grads = None
-                    self.last = {"radii": radii}
-                    return out
-                self._nacc = 0
-                grads = self._acc
-                if self.exchange_feat is not None:
-                    self.exchange_feat.launch([grads[i] for i in self.feat_pos])
-            self._grads = grads
-            if self.exchange is not None:
-                if self.exchange_feat is not None:
-                    self.exchange.launch([grads[i] for i in self.rest_pos])
-                else:                                      # sharded: one reduce-scatter over the dense tensors + the window all-to-all
-                    self.opt.launch_exchange(grads, windows)
+            pending = self._submit(grads, windows)
         self.last = {"radii": radii}
-        self._note_regularizers()
+        if pending:
+            self._note_regularizers()
         return out
+
+    def _submit(self, grads, windows=None):
+        """A view's 15 gradients on their way to the optimizer step: added to the group's accumulators (views_per_step > 1) and, with
+        the group's last view, put on the wire (the feature gradients of a single-view step are there already).  windows: the sharded
+        optimizer's keyframe windows.  False: accumulated only, no step follows this view."""
+        if self.k > 1:
+            # views 1 .. k-1 of the group: added to the accumulators, nothing goes on the wire, no optimizer step follows
+            if self._acc is None:
+                self._acc = [torch.zeros_like(p) for p in self.params]
+            if self._nacc == 0:
+                if self.exchange_feat is not None:
+                    self.exchange_feat.wait()            # (the previous group's collectives own the accumulators until here)
+                for a, g_ in zip(self._acc, grads):
+                    a.copy_(g_)
+            else:
+                torch._foreach_add_(self._acc, list(grads))
+            self._nacc += 1
+            if self._nacc < self.k:
+                self._grads = None
+                return False
+            self._nacc = 0
+            grads = self._acc
+            if self.exchange_feat is not None:
+                self.exchange_feat.launch([grads[i] for i in self.feat_pos])
+        self._grads = grads
+        if self.exchange is not None:
+            if self.exchange_feat is not None:
+                self.exchange.launch([grads[i] for i in self.rest_pos])
+            else:                                      # sharded: one reduce-scatter over the dense tensors + the window all-to-all
+                self.opt.launch_exchange(grads, windows)
+        return True
 
     def _note_regularizers(self):
         """The frame's regulariser weights and loss terms (at the parameters the frame was rendered with), on the main stream."""
@@ -363,14 +380,22 @@ class FrameTrainer:
 
     def _apply_optimizer(self):
         self._drain()
+        # the step's regulariser weights; the terms are added HERE, after the exchange was drained: once per optimizer step, last, to the
+        # gradient summed over ranks and views (with views_per_step > 1 the accumulators are what was exchanged)
+        w = self._reg_w if self.regularizers is not None and self._reg_w is not None and any(self._reg_w) else None
         if self.mode == "sharded":
-            self.opt.step()                                # (its exchange was launched by _run_frame: launch_exchange(grads, windows))
+            reg = None
+            if w is not None:                              # the owner of an element adds its term (dist.ShardedRAdam.step); sliced or dense alike
+                from .regularizers import REG_MOTION, REG_ROT, REG_STATIC
+                reg = {self.names.index(n): (kind, wt, self.params[self.names.index(n)].shape[0])        # rows: Ns, Nd, Nd -- the means' counts
+                       for n, kind, wt in (("_xyz_disp", REG_STATIC, w[0]), ("_xyz_motion", REG_MOTION, w[1]), ("_rotation_motion", REG_ROT, w[2]))}
+            self.opt.step(reg=reg)                         # (its exchange was launched by _run_frame: launch_exchange(grads, windows))
         else:
             from .optim import radam_step_raw, radam_step_sliced_raw, radam_step_sliced_reg_raw, REG_MOTION, REG_ROT
             self.steps += 1
-            w = self._reg_w if self.regularizers is not None and self._reg_w is not None and any(self._reg_w) else None
             if w is not None:
-                # dense gradients take their terms here (added to the frame's gradient buffers); sliced keyframe tensors in the step below
+                # dense gradients take their terms here (added to the frame's gradient buffers, which hold the sums over the ranks in mode
+                # "allreduce": ParamGradExchange reduces in place); sliced keyframe tensors in the step below, on every rank's window
                 from . import regularizers as reg
                 gi = [self._grads[self.names.index(n)] for n in ("_xyz_disp", "_xyz_motion", "_rotation_motion")]
                 if self.sliced:

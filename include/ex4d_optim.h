@@ -78,7 +78,8 @@ int ex4d_radam_step_sliced(const Ex4dRadamSlicedTensor *tensors, int32_t count, 
  * The regulariser gradient of a keyframe is a function of its Gaussian's own row BEFORE the update, so each workgroup owns whole rows,
  * stages them in LDS and forms the gradient there: the dense gradient never exists in memory, the traffic stays 24 B per element plus
  * the windows.  Its coefficient is reg_weight / (reg_rows (K-1)), on the host in double, cast to float32; reg_rows is the model's full
- * dynamic count (`rows` may be a row range of it).  K = 1 or reg_weight = 0: no term, a plain sliced step.
+ * dynamic count (`rows` may be a row range of it: the whole rows a rank of the sharded optimizer owns, with the windows of all ranks
+ * in rank order -- the term is added once, by the owner, after the exchange).  K = 1 or reg_weight = 0: no term, a plain sliced step.
  * Bit-identical to ex4d_radam_step on (windows scattered into zeros, then ex4d_reg_backward with accumulate = 1).
  * A K so large that four rows do not fit the staging LDS returns EX4D_ERR_ARG (ex4d_radam_sliced_reg_rows gives 0): take the dense path. */
 typedef struct Ex4dRadamSlicedRegTensor {

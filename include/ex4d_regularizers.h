@@ -11,6 +11,10 @@
  * 1/Ns and 1/(Nd (K-1)).  ex4d_radam_step_sliced_reg (ex4d_optim.h) therefore forms the keyframe terms inside the optimizer step from
  * the row it is about to update; the functions here are the stand-alone form (loss value, dense gradients for autograd and for the
  * dense-gradient paths).  Both share one per-row arithmetic (csrc/ex4d_reg_rows.h): the same bits either way.
+ *
+ * Several ranks: the term is added ONCE per optimizer step, last, to the gradient summed over ranks and views -- never before the
+ * exchange.  The replicated optimizer adds ex4d_reg_backward to the reduced buffers (or runs the fused step on the gathered windows);
+ * the sharded optimizer adds ex4d_reg_backward_range to the element range it owns, or hands its owned rows to the fused step.
  */
 #ifndef EX4D_REGULARIZERS_H_INCLUDED
 #define EX4D_REGULARIZERS_H_INCLUDED
@@ -41,6 +45,18 @@ int ex4d_reg_forward(const float *xyz_disp, int64_t Ns, const float *xyz_motion,
 int ex4d_reg_backward(const float *xyz_disp, float *g_xyz_disp, int64_t Ns, const float *xyz_motion, float *g_xyz_motion,
                       const float *rotation_motion, float *g_rotation_motion, int64_t Nd, int32_t K,
                       double static_reg, double motion_reg, double rot_reg, const float *upstream, int32_t accumulate, void *stream);
+
+/* The gradient of ONE term over a flat element range [lo, hi) of its tensor: what a rank of the sharded optimizer adds to the summed
+ * gradient of the elements it owns (dist.ShardedRAdam cuts dense tensors into element ranges, in the middle of rows and keyframes).
+ * kind 1: motion_reg on [rows,K,3], 2: rot_reg on [rows,K,4] (reg_kind of ex4d_optim.h), 3: static_reg on [rows,3] (K is ignored).
+ * param: base of the WHOLE tensor; rows: its full row count, the one of the mean's 1/rows or 1/(rows (K-1)); grad[0] belongs to
+ * element lo (a view of a shard buffer).  A row the range cuts is read whole, elements outside [lo, hi) are not written.
+ * Every element gets the bits ex4d_reg_backward gives it (upstream NULL): the same per-row arithmetic, the same coefficient.
+ * accumulate = 0: every element of the range is written once (zeros where the term is off: weight 0, K = 1); 1: added.
+ * lo == hi: EX4D_OK without a launch; lo < 0, hi > numel, lo > hi or an unknown kind: EX4D_ERR_ARG.  One launch of plain vector
+ * stores, no atomics, capturable in a graph. */
+int ex4d_reg_backward_range(int32_t kind, const float *param, int64_t rows, int32_t K, int64_t lo, int64_t hi, float *grad, double weight,
+                            int32_t accumulate, void *stream);
 
 #ifdef __cplusplus
 }
