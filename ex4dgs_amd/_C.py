@@ -422,6 +422,17 @@ def get_option(name):
     return int(load().ex4d_get_option(name.encode()))
 
 
+SAMPLE_SORT_STATS = ("empty", "skipped", "packed", "pairs", "memory", "memory_gaussians", "largest", "distinct_splitters")
+
+
+def sample_sort_stats(reset=True):
+    """Developer census of the sample depth sort (ex4d_debug_sample_sort; option "depth_sort_sample_stats" = 1): a dict of how its
+    buckets were handled since the last reset, keyed by SAMPLE_SORT_STATS."""
+    buf = (C.c_ulonglong * 8)()
+    _abi.call("ex4d_debug_sample_sort", buf, int(bool(reset)))
+    return dict(zip(SAMPLE_SORT_STATS, (int(x) for x in buf)))
+
+
 def bwd_stats(reset=True, extended=False):
     """Developer counters of the compositing backward's variant 8 (ex4d_debug_bwd_stats): batches, valid Gaussians, steps run,
     steps skipped, contributing (pixel, Gaussian) pairs, Gaussians with a contributing pair, ... ; extended=True: the 16 counters of

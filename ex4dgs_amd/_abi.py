@@ -160,6 +160,7 @@ PROTOTYPES = {
         _status("ex4d_debug_bwd_stats", P(C.c_ulonglong), cint),
         _status("ex4d_debug_bwd_stats16", P(C.c_ulonglong), cint),
         _status("ex4d_debug_rows_prof", P(C.c_ulonglong), cint),
+        _status("ex4d_debug_sample_sort", P(C.c_ulonglong), cint),
         _value("ex4d_profile_enable", None, cint),
         _value("ex4d_profile_read", cint, cint, P(f32), P(text), cint))),
     "ex4d_attributes.h": ("ex4d_attributes_last_error", (

@@ -80,6 +80,11 @@ std::atomic<int> g_depth_msd_bits{0};       // "depth_sort_msd_bits": 0 (default
 std::atomic<int> g_readback_side{1};        // "readback_side_stream": 1 (default, round 6) = the synchronous forward's read-back copy runs on a side stream; 0 = on the caller's stream (rounds 1-5)
 std::atomic<int> g_depth_local_cap{0};      // "depth_sort_local_cap": largest bucket the MSD depth sort finishes in LDS (0 = the kernel's capacity; tests force the through-memory path with a small value)
 std::atomic<int> g_depth_local_threads{0};  // "depth_sort_local_threads": 256 / 512 = workgroup size of the depth sort's bucket kernel, 0 = by Gaussian count
+// "depth_sort_sample": 1 = every frame the MSD sort applies to is ordered by the sample sort (ex4d_binning.hip: buckets of equal count,
+// no host feedback), synchronous, asynchronous and captured calls alike; such a frame neither reads nor writes the auto mode's watch word
+std::atomic<int> g_depth_sample{0};
+std::atomic<int> g_depth_sample_frames{0};  // "depth_sort_sample_frames" (read-only): forwards that took the sample sort since the option was set
+std::atomic<int> g_depth_sample_stats{0};   // "depth_sort_sample_stats": 1 = the sample sort's kernels count their buckets per path (ex4d_debug_sample_sort)
 std::atomic<int> g_geom_debug{0};    // "geom_debug_arrays": also write cov3D[P,6] and tiles_touched[P] into the geometry buffer (tests)      // "binning_tile_ids": also write the sorted tile ids (tests, debugging)
 thread_local char g_err[512] = "";
 
@@ -350,7 +355,9 @@ static int forward_impl(
     // per-Gaussian kernel leaves that range in the frame flags), the invisible key gets the last digit to itself
     int msd_mode = g_depth_msd.load(std::memory_order_relaxed);
     uint32_t *msd_watch = nullptr;
+    const bool sample_depth = g_depth_sample.load(std::memory_order_relaxed) != 0 && packed_rects && ex4d_depth_sort_msd_applies((uint32_t)P, key_bits);
     if (!(packed_rects && ex4d_depth_sort_msd_applies((uint32_t)P, key_bits))) msd_mode = 0;
+    else if (sample_depth) msd_mode = 1;          // (hands over what the MSD sort with the streaming tile scan does; the watch word is not touched)
     else if (msd_mode == 3) msd_mode = depth_sort_auto_msd(stream, async, &msd_watch) ? 2 : 0;
     const bool msd_depth = msd_mode != 0;
     int msd_bits = ex4d_depth_sort_msd_bits((uint32_t)P, key_bits);      // width of its top digit: 9 bits up to 1.3 M Gaussians, 10 beyond (round 6)
@@ -378,7 +385,7 @@ static int forward_impl(
     STAGE(ex4d_launch_preprocess_fwd(*prm, means3D, dir3D, scales, rotations, opacities, shs, cov3D_precomp, colors_precomp,
                                      viewmatrix, projmatrix, campos, radii, gw, g.total + 1, split,
                                      keys0, (uint32_t *)nullptr, key_base, key_invisible, packed_rects ? g.rects4 : nullptr, stream,
-                                     msd_depth ? reinterpret_cast<uint32_t *>(g.key_ranges) : nullptr, async), prm, stream);
+                                     (msd_depth && !sample_depth) ? reinterpret_cast<uint32_t *>(g.key_ranges) : nullptr, async), prm, stream);
     MARK(0, "preprocess_fwd");
     // the one read-back the reference also has (rasterizer_impl.cu:298-299), started here: the instance count was summed by
     // the preprocess kernel and travels to a pinned host word while the depth sort below keeps the GPU busy
@@ -405,10 +412,18 @@ static int forward_impl(
     const bool fused_scan = msd_mode == 2 && !rows_sort;
     const bool lsd_gather = !msd_depth && rows_sort && packed_rects;      // LSD depth sort in front of the row-segment sort: its last pass hands over the rects
     if (msd_depth) {
-        STAGE(ex4d_depth_sort_msd(g.sort_keys_a, g.sort_vals_a, g.rects4, g.sort_keys_b, g.depth_order, g.rects4_b, (uint32_t)P, key_invisible,
-                                  g.total, g.key_ranges, g.sort_hist, g.bucket_starts, (uint32_t)g_depth_local_cap.load(std::memory_order_relaxed), stream,
-                                  fused_scan ? g.sorted_offsets : nullptr, fused_scan ? g.bucket_sums : nullptr, T, (fused_scan || rows_sort) ? im.ranges : nullptr,
-                                  g_depth_local_threads.load(std::memory_order_relaxed), msd_watch, msd_bits), prm, stream);
+        if (sample_depth) {
+            g_depth_sample_frames.fetch_add(1);
+            STAGE(ex4d_depth_sort_sample(g.sort_keys_a, g.sort_vals_a, g.rects4, g.sort_keys_b, g.depth_order, g.rects4_b, (uint32_t)P, key_invisible, key_bits,
+                                         g.sort_hist, g.bucket_starts, g.bucket_sums, (uint32_t)g_depth_local_cap.load(std::memory_order_relaxed), stream,
+                                         T, rows_sort ? im.ranges : nullptr, g_depth_local_threads.load(std::memory_order_relaxed),
+                                         g_depth_sample_stats.load(std::memory_order_relaxed) != 0), prm, stream);
+        } else {
+            STAGE(ex4d_depth_sort_msd(g.sort_keys_a, g.sort_vals_a, g.rects4, g.sort_keys_b, g.depth_order, g.rects4_b, (uint32_t)P, key_invisible,
+                                      g.total, g.key_ranges, g.sort_hist, g.bucket_starts, (uint32_t)g_depth_local_cap.load(std::memory_order_relaxed), stream,
+                                      fused_scan ? g.sorted_offsets : nullptr, fused_scan ? g.bucket_sums : nullptr, T, (fused_scan || rows_sort) ? im.ranges : nullptr,
+                                      g_depth_local_threads.load(std::memory_order_relaxed), msd_watch, msd_bits), prm, stream);
+        }
         MARK(0, "depth_sort");
         // 3. instance offsets in depth order + total: the rects arrive in depth order (rects4_b), nothing to gather
         if (!fused_scan && !rows_sort) {
@@ -672,6 +687,8 @@ int ex4d_set_option(const char *name, int value)
     if (name && !strcmp(name, "geom_debug_arrays") && (value == 0 || value == 1)) { g_geom_debug.store(value); return EX4D_OK; }
     if (name && !strcmp(name, "preprocess_fast_path") && (value == 0 || value == 1)) { ex4d_set_preprocess_fast(value); return EX4D_OK; }
     if (name && !strcmp(name, "depth_sort_msd") && value >= 0 && value <= 3) { g_depth_msd.store(value); g_depth_watch.reset(); return EX4D_OK; }
+    if (name && !strcmp(name, "depth_sort_sample") && (value == 0 || value == 1)) { g_depth_sample.store(value); g_depth_sample_frames.store(0); return EX4D_OK; }
+    if (name && !strcmp(name, "depth_sort_sample_stats") && (value == 0 || value == 1)) { g_depth_sample_stats.store(value); return EX4D_OK; }
     if (name && !strcmp(name, "depth_sort_local_cap") && value >= 0 && value <= 8192) { g_depth_local_cap.store(value); return EX4D_OK; }
     if (name && !strcmp(name, "readback_side_stream") && (value == 0 || value == 1)) { g_readback_side.store(value); return EX4D_OK; }
     if (name && !strcmp(name, "depth_sort_msd_bits") && (value == 0 || value == EX4D_DLS_MSD_BITS - 1 || value == EX4D_DLS_MSD_BITS)) { g_depth_msd_bits.store(value); return EX4D_OK; }
@@ -681,6 +698,7 @@ int ex4d_set_option(const char *name, int value)
 
 int ex4d_debug_bwd_stats(unsigned long long *out8, int reset) { return ex4d_bwd_stats(out8, 8, reset) == hipSuccess ? EX4D_OK : EX4D_ERR_HIP; }
 int ex4d_debug_rows_prof(unsigned long long *out8, int reset) { return ex4d_rows_prof(out8, reset) == hipSuccess ? EX4D_OK : EX4D_ERR_HIP; }
+int ex4d_debug_sample_sort(unsigned long long *out8, int reset) { return ex4d_sample_sort_stats(out8, reset) == hipSuccess ? EX4D_OK : EX4D_ERR_HIP; }
 int ex4d_debug_bwd_stats16(unsigned long long *out16, int reset) { return ex4d_bwd_stats(out16, 16, reset) == hipSuccess ? EX4D_OK : EX4D_ERR_HIP; }
 
 int ex4d_get_option(const char *name)
@@ -699,6 +717,9 @@ int ex4d_get_option(const char *name)
     if (name && !strcmp(name, "depth_sort_msd")) return g_depth_msd.load();
     if (name && !strcmp(name, "depth_sort_hold")) return g_depth_watch.hold.load();        // (read-only) auto mode: frames left on the LSD sort
     if (name && !strcmp(name, "depth_sort_trips")) return g_depth_watch.trips.load();      // (read-only) auto mode: oversize buckets seen since the option was set
+    if (name && !strcmp(name, "depth_sort_sample")) return g_depth_sample.load();
+    if (name && !strcmp(name, "depth_sort_sample_frames")) return g_depth_sample_frames.load();      // (read-only)
+    if (name && !strcmp(name, "depth_sort_sample_stats")) return g_depth_sample_stats.load();
     if (name && !strcmp(name, "depth_sort_local_cap")) return g_depth_local_cap.load();
     if (name && !strcmp(name, "readback_side_stream")) return g_readback_side.load();
     if (name && !strcmp(name, "depth_sort_msd_bits")) return g_depth_msd_bits.load();

@@ -1043,6 +1043,324 @@ __global__ __launch_bounds__(256) void tile_ranges_kernel(uint32_t R, const uint
     if (i == R - 1) ranges[cur].y = R;
 }
 
+// ---------------------------------------------------------------- depth sort by sampling: buckets of equal COUNT (option "depth_sort_sample")
+// The MSD sort above cuts its buckets by key VALUE: a wall of Gaussians at one depth lands in one bucket, and one workgroup sorts it
+// through global memory.  Here the buckets are cut at splitters sampled from the frame's own keys, so a bucket holds ~P / BINS
+// Gaussians whatever the scene is.  Five launches, grids constant on the host, no word for the host: capturable.
+//   splitters  ONE workgroup reads the keys at ids 0, stride, 2 stride, ... (stride = ceil(P / 8192): at most 8192 of them, every key
+//              for P <= 8192), sorts them in LDS (the passes of the bucket kernel, on whole keys) and takes BINS - 2 quantiles:
+//              spl[j] = sorted[(j + 1) ns / (BINS - 1)], j < BINS - 2, followed by the invisible key TWICE.  A function of (keys, P,
+//              invisible key) alone.  The bucket table `ub` follows from the sorted list spl: a value that occurs once closes the bucket
+//              (previous value, v]; a value that occurs more than once gets the bucket (previous value, v) and a bucket of its own, [v, v]
+//              -- a repeated splitter is the footprint of a run of equal keys the sample met more than once, and the invisible key
+//              always is one.  Distinct values + repeated values <= list length = BINS.  ub holds the upper bounds in the doubled space
+//              K = 2 key + 1 (2 v closes "below v", 2 v + 1 closes "up to v"; keys are < 2^28 where the sort applies), padded with ~0:
+//              bucket(key) = number of entries below 2 key + 1.
+//   partition  histogram -> row scan -> scatter as in the MSD sort (stable: dls_rank, ballots or LDS atomics), the digit by a binary
+//              search of the table in LDS.
+//   buckets    a workgroup per bucket.  Its keys lie in [klo, khi] = what (ub[b - 1], ub[b]] admits.  klo == khi: every key is equal, the
+//              stable partition ordered it (every equality bucket, the invisible one among them: no special case).  Else the bucket is
+//              sorted on key - klo: on packed words (key << IDX_BITS | arrival index) where the span's bits fit beside the index, on
+//              (key, index) pairs in two LDS arrays where they do not (a sparse depth range: few keys, wide span) -- both in LDS, with
+//              the passes the span's own width needs; a bucket beyond `cap` through memory (the sample is not a proof).
+#define SS_SAMPLE 8192
+__device__ unsigned long long g_ss_stats[8];      // developer census (option "depth_sort_sample_stats"): ex4d_debug_sample_sort
+
+template <int BINS>
+__device__ __forceinline__ uint32_t ss_bucket_of(const uint32_t *ub, uint32_t key)
+{
+    const uint32_t K = 2u * key + 1u;
+    uint32_t i = 0;
+#pragma unroll
+    for (uint32_t step = BINS / 2; step > 0; step >>= 1) if (ub[i + step - 1u] < K) i += step;      // (the last real entry is 2 inv + 1 >= K: i <= BINS - 1)
+    return i;
+}
+
+template <int BINS>
+__global__ __launch_bounds__(512) void ss_splitter_kernel(const uint32_t *__restrict__ keys, uint32_t n, uint32_t inv_key, int key_bits,
+    uint32_t *__restrict__ table, unsigned long long *__restrict__ stats)
+{
+    __shared__ DlsLds<512> L;
+    __shared__ uint32_t spl[BINS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t stride = (n + SS_SAMPLE - 1u) / SS_SAMPLE;
+    const uint32_t ns = (n + stride - 1u) / stride;                 // 1 .. SS_SAMPLE
+    {
+        uint32_t k[DLS_ITEMS];
+#pragma unroll
+        for (int j = 0; j < DLS_ITEMS; j++) { const uint32_t p = tid + j * 512; k[j] = p < ns ? keys[p * stride] : 0u; }
+#pragma unroll
+        for (int j = 0; j < DLS_ITEMS; j++) { const uint32_t p = tid + j * 512; if (p < ns) L.buf[p] = k[j]; }
+    }
+    __syncthreads();
+    const int npass = (key_bits + 8) / 9;
+    const uint32_t m = ((ns + 8 * 64 - 1) / (8 * 64)) * 64;
+    for (int pass = 0, lo = 0; pass < npass; pass++) {
+        const int nbits = dls_pass_bits(key_bits, lo, npass, pass);
+        dls_lds_pass<512, 0>(L, ns, m, lo, nbits);
+        lo += nbits;
+    }
+    constexpr uint32_t NSPL = BINS - 2;
+    for (uint32_t j = tid; j < (uint32_t)BINS; j += 512) spl[j] = j < NSPL ? L.buf[((j + 1u) * ns) / (NSPL + 1u)] : inv_key;
+    __syncthreads();
+    // the table: thread t owns the PER consecutive list entries PER t ...; x = entries emitted | distinct values << 16
+    constexpr int PER = BINS / 512;
+    uint32_t v[PER], c[PER], x = 0;
+#pragma unroll
+    for (int q = 0; q < PER; q++) {
+        const uint32_t j = tid * PER + q;
+        v[q] = spl[j];
+        const bool first = j == 0u || spl[j - 1u] != v[q];
+        const bool rep = first && j + 1u < (uint32_t)BINS && spl[j + 1u] == v[q];
+        c[q] = first ? (rep ? 2u : 1u) : 0u;
+        x += c[q] + (first ? 0x10000u : 0u);
+    }
+    const uint32_t own = x;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const uint32_t y = __shfl_up(x, o, 64); if (lane >= o) x += y; }
+    if (lane == 63) L.scan_tmp[wave] = x;
+    __syncthreads();
+    uint32_t excl = x - own, total = 0;
+    for (int w = 0; w < 8; w++) { const uint32_t t = L.scan_tmp[w]; if (w < wave) excl += t; total += t; }
+    uint32_t off = excl & 0xFFFFu;
+#pragma unroll
+    for (int q = 0; q < PER; q++) {
+        if (c[q] == 2u) { table[off] = 2u * v[q]; table[off + 1u] = 2u * v[q] + 1u; }
+        else if (c[q] == 1u) table[off] = 2u * v[q] + 1u;
+        off += c[q];
+    }
+    for (uint32_t j = (total & 0xFFFFu) + tid; j < (uint32_t)BINS; j += 512) table[j] = 0xFFFFFFFFu;
+    if (stats && tid == 0) atomicAdd(&stats[7], (unsigned long long)(total >> 16));
+}
+
+template <int ITEMS, int BINS>
+__global__ __launch_bounds__(RS_THREADS) void ss_histogram_kernel(const uint32_t *__restrict__ keys, uint32_t n, uint32_t nblocks,
+    uint32_t *__restrict__ hist, const uint32_t *__restrict__ table)
+{
+    __shared__ uint32_t h[BINS];
+    __shared__ uint32_t ub[BINS];
+    for (int b = threadIdx.x; b < BINS; b += RS_THREADS) { h[b] = 0; ub[b] = table[b]; }
+    const uint32_t base = blockIdx.x * (RS_THREADS * ITEMS);
+    uint32_t k[ITEMS];
+    if (base < n) {
+#pragma unroll
+        for (int it = 0; it < ITEMS; it++) {
+            const uint32_t i = base + it * RS_THREADS + threadIdx.x;
+            k[it] = keys[i < n ? i : n - 1];
+        }
+    }
+    __syncthreads();
+    if (base < n) {
+#pragma unroll
+        for (int it = 0; it < ITEMS; it++) {
+            const uint32_t i = base + it * RS_THREADS + threadIdx.x;
+            if (i < n) atomicAdd(&h[ss_bucket_of<BINS>(ub, k[it])], 1u);
+        }
+    }
+    __syncthreads();
+    for (int b = threadIdx.x; b < BINS; b += RS_THREADS) hist[(size_t)b * nblocks + blockIdx.x] = h[b];
+}
+
+// the stable partition of the (key, id, packed rect) triples by bucket: rs_scatter_kernel's MODE 3 with the table's digit (the ids are
+// the item indices; workgroup 0 leaves the first output position of every bucket in bucket_starts)
+template <int ITEMS, int BINS>
+__global__ __launch_bounds__(RS_THREADS) void ss_scatter_kernel(const uint32_t *__restrict__ keys_in, const uint32_t *__restrict__ rects_in,
+    uint32_t *__restrict__ keys_out, uint32_t *__restrict__ vals_out, uint32_t *__restrict__ rects_out, uint32_t n, uint32_t nblocks,
+    const uint32_t *__restrict__ hist, const uint32_t *__restrict__ table, uint32_t *__restrict__ bucket_starts)
+{
+    constexpr uint32_t CHUNK = RS_THREADS * ITEMS;
+    constexpr int NBITS = BINS == 512 ? 9 : 10, BPT = BINS / RS_THREADS;
+    static_assert(BINS == 512 || BINS == 1024, "bucket counts of the sample sort");
+    if (blockIdx.x * CHUNK >= n) return;
+    __shared__ uint32_t wave_cnt[4][BINS];
+    __shared__ uint32_t local_start[BINS];
+    __shared__ uint32_t global_base[BINS];
+    __shared__ uint32_t ub[BINS];
+    __shared__ uint32_t scan_tmp[4];
+    __shared__ uint2 stage[CHUNK];
+    __shared__ uint32_t stage_r[CHUNK];
+    static_assert(sizeof(uint32_t) * (7 * BINS + 4) + sizeof(uint32_t) * 3 * CHUNK <= 80 * 1024, "ss_scatter_kernel: static LDS beyond 80 KB");
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int i = tid; i < BINS; i += RS_THREADS) { ub[i] = table[i]; wave_cnt[0][i] = 0; wave_cnt[1][i] = 0; wave_cnt[2][i] = 0; wave_cnt[3][i] = 0; }
+    const uint32_t block_first = blockIdx.x * CHUNK, block_end = n;
+    const uint32_t base = block_first + wave * (CHUNK / 4);
+    uint32_t pre_gt[BPT], pre_hb[BPT];
+#pragma unroll
+    for (int k = 0; k < BPT; k++) {
+        const int d = tid * BPT + k;
+        pre_gt[k] = hist[(size_t)BINS * nblocks + d];
+        pre_hb[k] = hist[(size_t)d * nblocks + blockIdx.x];
+    }
+    uint32_t key[ITEMS], pos[ITEMS], rct[ITEMS], dig[ITEMS];
+#pragma unroll
+    for (int it = 0; it < ITEMS; it++) {
+        const uint32_t i = base + it * 64 + lane;
+        const uint32_t ic = i < block_end ? i : block_end - 1;
+        key[it] = keys_in[ic];
+        rct[it] = rects_in[ic];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int it = 0; it < ITEMS; it++) {
+        const uint32_t i = base + it * 64 + lane;
+        dig[it] = ss_bucket_of<BINS>(ub, key[it]);
+        pos[it] = dls_rank<NBITS>(wave_cnt[wave], dig[it], NBITS, i < block_end, lane);
+    }
+    __syncthreads();
+    {
+        uint32_t c[BPT][4], tot[BPT];
+        uint32_t tsum = 0, gsum = 0;
+#pragma unroll
+        for (int k = 0; k < BPT; k++) {
+            const int d = tid * BPT + k;
+#pragma unroll
+            for (int w = 0; w < 4; w++) c[k][w] = wave_cnt[w][d];
+            tot[k] = c[k][0] + c[k][1] + c[k][2] + c[k][3];
+            tsum += tot[k]; gsum += pre_gt[k];
+        }
+        uint32_t x = tsum, gx = gsum;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t y = __shfl_up(x, o, 64), gy = __shfl_up(gx, o, 64);
+            if (lane >= o) { x += y; gx += gy; }
+        }
+        if (lane == 63) { scan_tmp[wave] = x; local_start[wave] = gx; }          // (local_start: free until the loop below)
+        __syncthreads();
+        uint32_t ls = x - tsum, gb = gx - gsum;
+        for (int w = 0; w < wave; w++) { ls += scan_tmp[w]; gb += local_start[w]; }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < BPT; k++) {
+            const int d = tid * BPT + k;
+            local_start[d] = ls;
+            global_base[d] = gb + pre_hb[k];
+            if (blockIdx.x == 0) bucket_starts[d] = gb;
+            wave_cnt[0][d] = ls; wave_cnt[1][d] = ls + c[k][0]; wave_cnt[2][d] = ls + c[k][0] + c[k][1]; wave_cnt[3][d] = ls + c[k][0] + c[k][1] + c[k][2];
+            ls += tot[k]; gb += pre_gt[k];
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int it = 0; it < ITEMS; it++) {
+        const uint32_t i = base + it * 64 + lane;
+        if (i < block_end) {
+            const uint32_t slot = wave_cnt[wave][dig[it]] + pos[it];
+            stage[slot] = make_uint2(key[it], i);
+            stage_r[slot] = rct[it];
+        }
+    }
+    __syncthreads();
+    const uint32_t count = (block_end - block_first) < CHUNK ? (block_end - block_first) : CHUNK;
+#pragma unroll 4
+    for (uint32_t p = tid; p < count; p += RS_THREADS) {
+        const uint2 kv = stage[p];
+        const uint32_t d = ss_bucket_of<BINS>(ub, kv.x);
+        const uint32_t dst = global_base[d] + (p - local_start[d]);
+        keys_out[dst] = kv.x; vals_out[dst] = kv.y; rects_out[dst] = stage_r[p];
+    }
+}
+
+// (the arrival index of the pair path in 16 bits: 64 KB with 512 threads, two workgroups per CU -- every bucket of 1.0 M Gaussians resident at once)
+template <int THREADS> struct SsLds { DlsLds<THREADS> L; uint16_t idx[THREADS * DLS_ITEMS]; };
+
+// one stable LSD pass over the n (key, arrival index) pairs in (L.buf, idx) on the digit (key >> lo) & (2^nbits - 1)
+template <int THREADS>
+__device__ __forceinline__ void ss_pair_pass(SsLds<THREADS> &S, uint32_t n, uint32_t m, int lo, int nbits)
+{
+    DlsLds<THREADS> &L = S.L;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t mask = (1u << nbits) - 1u;
+    const uint32_t wbase = wave * m;
+    for (int i = lane; i < (1 << nbits); i += 64) L.cnt[wave][i] = 0;
+    dls_wave_sync();
+    uint32_t word[DLS_ITEMS], idx[DLS_ITEMS], pos[DLS_ITEMS];
+#pragma unroll
+    for (int it = 0; it < DLS_ITEMS; it++) {
+        word[it] = 0u; idx[it] = 0u; pos[it] = 0u;
+        if ((uint32_t)(it * 64) < m) {                    // (wave-uniform)
+            const uint32_t i = wbase + it * 64 + lane;
+            const bool valid = i < n;
+            word[it] = valid ? L.buf[i] : 0u;
+            idx[it] = valid ? S.idx[i] : 0u;
+            pos[it] = dls_rank<0>(L.cnt[wave], (word[it] >> lo) & mask, nbits, valid, lane);
+        }
+    }
+    __syncthreads();
+    dls_scan_counts(L, nbits);
+#pragma unroll
+    for (int it = 0; it < DLS_ITEMS; it++) {
+        if ((uint32_t)(it * 64) < m) {
+            const uint32_t i = wbase + it * 64 + lane;
+            if (i < n) { const uint32_t dst = L.cnt[wave][(word[it] >> lo) & mask] + pos[it]; L.buf[dst] = word[it]; S.idx[dst] = (uint16_t)idx[it]; }
+        }
+    }
+    __syncthreads();
+}
+
+// census cells (stats): [0] empty buckets, [1] buckets skipped (one key value, or one Gaussian), [2] sorted on packed words, [3] on pairs,
+// [4] through memory, [5] Gaussians in those, [6] largest bucket that admits more than one key value, [7] distinct splitters (splitter kernel)
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void ss_bucket_kernel(uint32_t *kb, uint32_t *vb, uint32_t *rb, uint32_t *ka, uint32_t *va, uint32_t *ra,
+    const uint32_t *__restrict__ starts, const uint32_t *__restrict__ totals, const uint32_t *__restrict__ table, uint32_t cap,
+    int T, uint2 *__restrict__ ranges, unsigned long long *__restrict__ stats)
+{
+    constexpr int DLS_THREADS = THREADS, DLS_WAVES = THREADS / 64, DLS_CAP = THREADS * DLS_ITEMS, IDX_BITS = DlsLds<THREADS>::IDX_BITS;
+    __shared__ SsLds<THREADS> S;
+    DlsLds<THREADS> &L = S.L;
+    const uint32_t b = blockIdx.x;
+    const int tid = threadIdx.x;
+    if (ranges) for (int i = b * DLS_THREADS + tid; i < T; i += gridDim.x * DLS_THREADS) ranges[i] = make_uint2(0u, 0u);
+    const uint32_t n = totals[b], s = starts[b];
+    if (n == 0u) { if (stats && tid == 0) atomicAdd(&stats[0], 1ull); return; }
+    const uint32_t ub_prev = b ? table[b - 1u] : 0u, ub_cur = table[b];
+    const uint32_t klo = (ub_prev + 1u) >> 1, khi = (ub_cur - 1u) >> 1;      // 2 key + 1 in (ub_prev, ub_cur]
+    const uint32_t span = khi - klo;
+    const int rem = span ? 32 - __builtin_clz(span) : 0;
+    if (stats && tid == 0 && span) atomicMax(&stats[6], (unsigned long long)n);
+    if (n < 2u || span == 0u) { if (stats && tid == 0) atomicAdd(&stats[1], 1ull); return; }
+    if (n > cap) {
+        if (stats && tid == 0) { atomicAdd(&stats[4], 1ull); atomicAdd(&stats[5], (unsigned long long)n); }
+        dls_sort_through_memory(L, kb + s, vb + s, rb + s, ka + s, va + s, ra + s, n, rem, klo);
+        return;
+    }
+    const bool packed = rem + IDX_BITS <= 32;
+    if (stats && tid == 0) atomicAdd(&stats[packed ? 2 : 3], 1ull);
+    {
+        uint32_t k[DLS_ITEMS];                           // every load in flight before the first LDS store
+#pragma unroll
+        for (int j = 0; j < DLS_ITEMS; j++) { const uint32_t p = tid + j * DLS_THREADS; k[j] = p < n ? kb[s + p] : 0u; }
+#pragma unroll
+        for (int j = 0; j < DLS_ITEMS; j++) {
+            const uint32_t p = tid + j * DLS_THREADS;
+            if (p < n) { if (packed) L.buf[p] = ((k[j] - klo) << IDX_BITS) | p; else { L.buf[p] = k[j] - klo; S.idx[p] = (uint16_t)p; } }
+        }
+    }
+    __syncthreads();
+    const int npass = (rem + 8) / 9;
+    const uint32_t m = ((n + DLS_WAVES * 64 - 1) / (DLS_WAVES * 64)) * 64;          // items per wave: a multiple of 64, <= 1024
+    for (int pass = 0, lo = 0; pass < npass; pass++) {
+        const int nbits = dls_pass_bits(rem, lo, npass, pass);
+        if (packed) dls_lds_pass<THREADS, 0>(L, n, m, IDX_BITS + lo, nbits);
+        else ss_pair_pass<THREADS>(S, n, m, lo, nbits);
+        lo += nbits;
+    }
+    // payload: position p takes the (id, rect) that arrived at index idx(p).  In place: every load lands before any store goes out
+    uint32_t v[DLS_ITEMS], r[DLS_ITEMS];
+#pragma unroll
+    for (int j = 0; j < DLS_ITEMS; j++) {
+        const uint32_t p = tid + j * DLS_THREADS;
+        v[j] = 0u; r[j] = 0u;
+        if (p < n) { const uint32_t idx = packed ? (L.buf[p] & (DLS_CAP - 1u)) : S.idx[p]; v[j] = vb[s + idx]; r[j] = rb[s + idx]; }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < DLS_ITEMS; j++) {
+        const uint32_t p = tid + j * DLS_THREADS;
+        if (p < n) { vb[s + p] = v[j]; rb[s + p] = r[j]; }
+    }
+}
+
 }  // namespace
 
 // ---- "rank_lds_atomics": -1 = probe once per device (default), 0 = ballot ranking, 1 = ranking by LDS atomics without asking
@@ -1189,6 +1507,56 @@ hipError_t ex4d_depth_sort_msd(uint32_t *ka, uint32_t *va, uint32_t *ra, uint32_
     if (msd_bits == EX4D_DLS_MSD_BITS - 1)
         return depth_sort_msd_launch<EX4D_DLS_MSD_BITS - 1>(ka, va, ra, kb, vb, rb, n, inv_key, flags, wave_ranges, hist, starts, local_cap, stream, local_incl, bucket_sums, T, ranges, local_threads, watch);
     return depth_sort_msd_launch<EX4D_DLS_MSD_BITS>(ka, va, ra, kb, vb, rb, n, inv_key, flags, wave_ranges, hist, starts, local_cap, stream, local_incl, bucket_sums, T, ranges, local_threads, watch);
+}
+
+// ---- sample depth sort (ss_* kernels above).  Arrays as for ex4d_depth_sort_msd; table: 1 << EX4D_DLS_MSD_BITS words of scratch (the
+// bucket table; the geometry buffer's bucket_sums, which only the MSD sort's fused tile scan uses); key_bits: bits of the invisible key.
+// 512 buckets up to 1.3 M Gaussians, 1024 beyond (the margin under the bucket kernel's capacity, as ex4d_depth_sort_msd_bits)
+template <int BINS>
+static hipError_t depth_sort_sample_launch(uint32_t *ka, uint32_t *va, uint32_t *ra, uint32_t *kb, uint32_t *vb, uint32_t *rb, uint32_t n, uint32_t inv_key, int key_bits,
+    uint32_t *hist, uint32_t *starts, uint32_t *table, uint32_t local_cap, hipStream_t stream, int T, uint2 *ranges, int local_threads, unsigned long long *stats)
+{
+    const uint32_t nb = rs_blocks_for(n);
+    if (local_threads != 256 && local_threads != 512) local_threads = 512;
+    const uint32_t kcap = (uint32_t)local_threads * DLS_ITEMS;
+    if (local_cap == 0 || local_cap > kcap) local_cap = kcap;
+    hipLaunchKernelGGL(ss_splitter_kernel<BINS>, dim3(1), dim3(512), 0, stream, (const uint32_t *)ka, n, inv_key, key_bits, table, stats);
+    if (rs_items_for(n) == RS_SMALL_ITEMS) {
+        hipLaunchKernelGGL((ss_histogram_kernel<RS_SMALL_ITEMS, BINS>), dim3(nb), dim3(RS_THREADS), 0, stream, (const uint32_t *)ka, n, nb, hist, (const uint32_t *)table);
+        hipLaunchKernelGGL(rs_scan_rows_kernel, dim3(BINS), dim3(256), 0, stream, nb, hist, (uint32_t)BINS);
+        hipLaunchKernelGGL((ss_scatter_kernel<RS_SMALL_ITEMS, BINS>), dim3(nb), dim3(RS_THREADS), 0, stream, (const uint32_t *)ka, (const uint32_t *)ra, kb, vb, rb, n, nb,
+            (const uint32_t *)hist, (const uint32_t *)table, starts);
+    } else {
+        hipLaunchKernelGGL((ss_histogram_kernel<RS_ITEMS, BINS>), dim3(nb), dim3(RS_THREADS), 0, stream, (const uint32_t *)ka, n, nb, hist, (const uint32_t *)table);
+        hipLaunchKernelGGL(rs_scan_rows_kernel, dim3(BINS), dim3(256), 0, stream, nb, hist, (uint32_t)BINS);
+        hipLaunchKernelGGL((ss_scatter_kernel<RS_ITEMS, BINS>), dim3(nb), dim3(RS_THREADS), 0, stream, (const uint32_t *)ka, (const uint32_t *)ra, kb, vb, rb, n, nb,
+            (const uint32_t *)hist, (const uint32_t *)table, starts);
+    }
+    if (local_threads == 256)
+        hipLaunchKernelGGL(ss_bucket_kernel<256>, dim3(BINS), dim3(256), 0, stream, kb, vb, rb, ka, va, ra, (const uint32_t *)starts, (const uint32_t *)(hist + (size_t)BINS * nb),
+            (const uint32_t *)table, local_cap, T, ranges, stats);
+    else
+        hipLaunchKernelGGL(ss_bucket_kernel<512>, dim3(BINS), dim3(512), 0, stream, kb, vb, rb, ka, va, ra, (const uint32_t *)starts, (const uint32_t *)(hist + (size_t)BINS * nb),
+            (const uint32_t *)table, local_cap, T, ranges, stats);
+    return hipGetLastError();
+}
+
+int ex4d_depth_sort_sample_bins(uint32_t n) { return n <= 1300000u ? 512 : 1024; }
+hipError_t ex4d_depth_sort_sample(uint32_t *ka, uint32_t *va, uint32_t *ra, uint32_t *kb, uint32_t *vb, uint32_t *rb, uint32_t n, uint32_t inv_key, int key_bits,
+    uint32_t *hist, uint32_t *starts, uint32_t *table, uint32_t local_cap, hipStream_t stream, int T, uint2 *ranges, int local_threads, bool census)
+{
+    if (n == 0) return hipSuccess;
+    unsigned long long *stats = nullptr;
+    if (census) { hipError_t e = hipGetSymbolAddress((void **)&stats, HIP_SYMBOL(g_ss_stats)); if (e != hipSuccess) return e; }
+    if (ex4d_depth_sort_sample_bins(n) == 512)
+        return depth_sort_sample_launch<512>(ka, va, ra, kb, vb, rb, n, inv_key, key_bits, hist, starts, table, local_cap, stream, T, ranges, local_threads, stats);
+    return depth_sort_sample_launch<1024>(ka, va, ra, kb, vb, rb, n, inv_key, key_bits, hist, starts, table, local_cap, stream, T, ranges, local_threads, stats);
+}
+hipError_t ex4d_sample_sort_stats(unsigned long long *out8, int reset)
+{
+    hipError_t e = hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_ss_stats), 8 * sizeof(unsigned long long));
+    if (e == hipSuccess && reset) { unsigned long long z[8] = { 0 }; e = hipMemcpyToSymbol(HIP_SYMBOL(g_ss_stats), z, sizeof(z)); }
+    return e;
 }
 
 // ---- MSD tile sort (see ts_block_table_kernel).  Applies when the tile id needs 9..16 bits and the Gaussian ids fit under the low digit.

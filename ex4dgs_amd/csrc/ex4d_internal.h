@@ -143,6 +143,13 @@ hipError_t ex4d_depth_sort_msd(uint32_t *ka, uint32_t *va, uint32_t *ra, uint32_
     uint32_t *watch = nullptr,                                                                   // watch: pinned host word set to 1 when a bucket exceeded the LDS capacity
     int msd_bits = EX4D_DLS_MSD_BITS);                                                           // EX4D_DLS_MSD_BITS or one less: ex4d_depth_sort_msd_bits()
 int ex4d_depth_sort_msd_bits(uint32_t n, int key_bits);      // digit width by Gaussian count (9 bits up to 1.3 M, 10 beyond)
+// Sample depth sort (ex4d_binning.hip, option "depth_sort_sample"): buckets of equal count cut at splitters sampled from the frame's keys;
+// hands over what the MSD sort with the streaming tile scan hands over.  table: 1 << EX4D_DLS_MSD_BITS words of scratch; key_bits: bits
+// of inv_key; census: count the buckets per path into the words ex4d_sample_sort_stats reads
+hipError_t ex4d_depth_sort_sample(uint32_t *ka, uint32_t *va, uint32_t *ra, uint32_t *kb, uint32_t *vb, uint32_t *rb, uint32_t n, uint32_t inv_key, int key_bits,
+    uint32_t *hist, uint32_t *starts, uint32_t *table, uint32_t local_cap, hipStream_t stream, int T, uint2 *ranges, int local_threads, bool census);
+int ex4d_depth_sort_sample_bins(uint32_t n);                 // 512 buckets up to 1.3 M Gaussians, 1024 beyond
+hipError_t ex4d_sample_sort_stats(unsigned long long *out8, int reset);
 // stable ranking by LDS atomics in the scatter kernels (ex4d_binning.hip): probed once per device, option "rank_lds_atomics"
 void ex4d_set_rank_lds(int v);
 int ex4d_get_rank_lds();

@@ -313,6 +313,17 @@ void ex4d_img_layout(int32_t W, int32_t H, Ex4dImgLayout *out);
  *                            Same order either way.
  *   "depth_sort_local_cap"   tests: largest bucket (0 = the kernel's capacity) the MSD depth sort finishes in LDS.
  *   "depth_sort_local_threads" 0 (default: 512 under the 9-bit digit and beyond 1.2 M Gaussians, else 256) / 256 / 512 = workgroup size of the MSD depth sort's bucket kernel.
+ *   "depth_sort_sample"      0 (default) = nothing changes; 1 = every frame the MSD depth sort applies to (see "depth_sort_msd") is ordered by the
+ *                            sample sort instead, whatever "depth_sort_msd" says, in synchronous, asynchronous and captured calls alike:
+ *                            buckets of equal COUNT cut at splitters sampled from the frame's own keys (the keys at ids 0, s, 2 s, ... with
+ *                            s = ceil(P / 8192), sorted by one workgroup in LDS, 510 -- beyond 1.3 M Gaussians 1022 -- quantiles of them and
+ *                            the invisible key; a splitter value that repeats gets a bucket of its own, which needs no sorting), a stable
+ *                            partition and one kernel that finishes every bucket in LDS.  Five launches, no word for the host: a wall of
+ *                            Gaussians at one depth costs what any other frame costs, and a graph replays it.  Same order bit for bit.
+ *                            Such a frame neither reads nor writes the auto mode's report word.  "depth_sort_local_cap" /
+ *                            "depth_sort_local_threads" (default here: 512) apply to its bucket kernel as well.
+ *                            "depth_sort_sample_frames" (read-only): forwards that took the sample sort since the option was last set.
+ *   "depth_sort_sample_stats" developer: 1 = the sample sort's kernels count how their buckets were handled (ex4d_debug_sample_sort).
  * Returns EX4D_OK / the value, or an error / -1. */
 int ex4d_set_option(const char *name, int value);
 int ex4d_get_option(const char *name);
@@ -326,6 +337,11 @@ int ex4d_debug_bwd_stats16(unsigned long long *out16, int reset);
 /* developer profile of the row-segment partition (option "rows_probe" = 1): shader-clock cycles per phase of its scatter kernel summed over
  * workgroups ([0] loads + count, [1] barrier scan, [2] placement, [3] width scan, [4] expansion, [5] write-out), [7] = workgroups */
 int ex4d_debug_rows_prof(unsigned long long *out8, int reset);
+/* developer census of the sample depth sort (option "depth_sort_sample_stats" = 1), summed over frames since the last reset: [0] empty
+ * buckets, [1] buckets skipped (all keys equal, or one Gaussian), [2] buckets sorted in LDS on packed words, [3] in LDS on (key, index)
+ * pairs, [4] through memory, [5] Gaussians in those, [6] largest bucket that admits more than one key value (a maximum, not a sum),
+ * [7] distinct splitter values (the invisible key included) */
+int ex4d_debug_sample_sort(unsigned long long *out8, int reset);
 
 /* Optional per-stage timing (hipEvents on the caller's stream, single host thread; used by bench.py).
  * ex4d_profile_read(which = 0 forward / 1 backward) waits for the last recorded call of that kind and
