@@ -16,7 +16,7 @@ namespace {
 std::atomic<bool> g_prof_on{false};
 // tuning knobs (ex4d_set_option): which compositing-backward kernel runs (ex4d_composite.hip: ex4d_launch_composite_bwd)
 std::atomic<int> g_bwd_variant{4};
-std::atomic<int> g_tile_ids{0};
+std::atomic<int> g_tile_ids{0};       // "binning_tile_ids": also write the sorted tile ids (tests, debugging)
 // "tile_sort_rows": 1 (default) = the tile lists come from the row-segment sort of round 6 (ex4d_rowsort.hip: no duplication kernel, no
 // instance offsets); 0 = duplication + the MSD-first pair sort of rounds 2-5.  Same point_list / ranges bit for bit.
 std::atomic<int> g_tile_rows{1};
@@ -85,7 +85,7 @@ std::atomic<int> g_depth_local_threads{0};  // "depth_sort_local_threads": 256 /
 std::atomic<int> g_depth_sample{0};
 std::atomic<int> g_depth_sample_frames{0};  // "depth_sort_sample_frames" (read-only): forwards that took the sample sort since the option was set
 std::atomic<int> g_depth_sample_stats{0};   // "depth_sort_sample_stats": 1 = the sample sort's kernels count their buckets per path (ex4d_debug_sample_sort)
-std::atomic<int> g_geom_debug{0};    // "geom_debug_arrays": also write cov3D[P,6] and tiles_touched[P] into the geometry buffer (tests)      // "binning_tile_ids": also write the sorted tile ids (tests, debugging)
+std::atomic<int> g_geom_debug{0};    // "geom_debug_arrays": also write cov3D[P,6] and tiles_touched[P] into the geometry buffer (tests)
 thread_local char g_err[512] = "";
 
 int fail(int code, const char *fmt, ...)

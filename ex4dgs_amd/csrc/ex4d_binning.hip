@@ -13,10 +13,19 @@
 // id), (2) emit their tile instances in that order, (3) stable-sort the instances by tile id alone.
 // Step (1) touches P elements (4 passes), step (3) needs only ceil(log2 T)=13..14 key bits = 2 passes
 // over R with 32-bit keys: ~5x less HBM traffic than the 6-pass 64-bit sort, bit-identical point_list.
-// All of it is integer work and HBM/latency bound; wave64 ballots give the stable in-wave ranks.
+// All of it is integer work and HBM/latency bound; wave64 ballots or LDS atomics give the stable in-wave ranks.
+//
+// Three things are said once and shared by every sort of this file: the stable in-wave rank (wave_rank), the stable partition of a
+// chunk by a digit (rs_histogram_kernel / rs_scan_rows_kernel / rs_scatter_kernel, written for a digit rule: DigitBits, DigitRange,
+// DigitTable) and the LDS sort that finishes a bucket (dls_load_packed, dls_sort_words, dls_permute_payload).  On top of them:
+//   the LSD depth sort       ex4d_radix_sort_pairs: passes of (key, value) pairs, DigitBits
+//   the MSD depth sort       ex4d_depth_sort_msd: one partition of (key, id, rect) triples by DigitRange + depth_local_sort_kernel
+//   the sample depth sort    ex4d_depth_sort_sample: ss_splitter_kernel, the same partition by DigitTable + ss_bucket_kernel
+//   the tile sorts           ex4d_tile_sort_msd (pass A + pass B, DigitBits) and ex4d_tile_sort_pass_b behind ex4d_rowsort.hip
 #include "ex4d_internal.h"
 #include <atomic>
 #include <mutex>
+#include <type_traits>
 
 // Round 6: stable ranking by LDS atomics.  The lanes of ONE ds_add_rtn_u32 instruction that hit the same LDS word receive their pre-op
 // values in ascending lane order on this part (tools/dev/micro/lds_atomic_order.hip: 4.2e9 lane-trials over every collision pattern, none
@@ -29,6 +38,70 @@ __device__ int ex4d_g_rank_lds = 0;
 
 namespace {
 
+// ---------------------------------------------------------------- stable in-wave ranking (every sort of this file ranks through it)
+__device__ __forceinline__ void wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// lanes of the wave that hold the same digit as this lane, among the valid ones (an invalid lane's own result means nothing).
+// NBITS > 0: digit width known at compile time -- the match loop unrolls (5 VALU per bit instead of a 12-slot loop body with its scalar
+// bookkeeping); 0: `nbits` at run time
+template <int NBITS>
+__device__ __forceinline__ uint64_t wave_peers(uint32_t d, int nbits, bool valid)
+{
+    // per bit keep the ballot if my bit is set, its complement otherwise -- written as ballot ^ (bit - 1) on 32-bit halves (plain
+    // xor/and; a select here compiles to the VOP2 v_cndmask that issues in ~24 cycles on gfx950 and made this loop the most expensive
+    // part of a scatter pass)
+    const uint64_t vmask = __builtin_amdgcn_ballot_w64(valid);
+    uint32_t plo = (uint32_t)vmask, phi = (uint32_t)(vmask >> 32);
+    if (NBITS > 0) {
+#pragma unroll
+        for (int b = 0; b < NBITS; b++) {
+            const uint64_t bal = __builtin_amdgcn_ballot_w64((d & (1u << b)) != 0u);
+            uint32_t flip;                                    // 0 when my bit is set, ~0 otherwise: my bit IS my lane's bit of the ballot
+            asm("v_cndmask_b32_e64 %0, -1, 0, %1" : "=v"(flip) : "s"(bal));
+            plo &= (uint32_t)bal ^ flip;
+            phi &= (uint32_t)(bal >> 32) ^ flip;
+            asm("" : "+v"(plo), "+v"(phi));                   // one fused and-xor per bit and half: keeps the chain from being regrouped into pairs
+        }
+    } else {
+        for (int b = 0; b < nbits; b++) {
+            const uint32_t bit = (d >> b) & 1u;
+            const uint64_t bal = __builtin_amdgcn_ballot_w64(bit != 0u);
+            const uint32_t flip = bit - 1u;                   // 0 when my bit is set, ~0 otherwise
+            plo &= (uint32_t)bal ^ flip;
+            phi &= (uint32_t)(bal >> 32) ^ flip;
+        }
+    }
+    return ((uint64_t)phi << 32) | plo;
+}
+// stable rank of this lane's item among the wave's items processed so far: returns the index among the wave's items of digit d
+// (wave-private counter row `cnt`), and bumps the counter.  All 64 lanes call it.  lds_rank: ex4d_g_rank_lds != 0, read once by the
+// caller (uniform)
+template <int NBITS>
+__device__ __forceinline__ uint32_t wave_rank(uint32_t *cnt, uint32_t d, int nbits, bool valid, bool lds_rank)
+{
+    if (lds_rank) return valid ? atomicAdd(&cnt[d], 1u) : 0u;      // the LDS atomic's return value (round 6; see ex4d_g_rank_lds above)
+    const uint64_t peers = wave_peers<NBITS>(d, nbits, valid);
+    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(peers >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)peers, 0u));      // peers below my lane
+    // every lane reads its digit's counter (the peers of a digit read ONE word: an LDS broadcast), then the first lane of every digit
+    // adds the digit's count -- a wave's LDS accesses execute in order, so the reads see the value before the update (round 5; rounds
+    // 1-4: the leader read, wrote and handed `before` to its peers through ds_bpermute: one more LDS round trip)
+    const uint32_t before = cnt[valid ? d : 0u];
+    if (valid && rank == 0) cnt[d] = before + (uint32_t)__popcll(peers);    // one lane per distinct digit: no two writers share an address
+    wave_sync();
+    return before + rank;
+}
+
+// the zero-fill of the tile ranges (cudaMemset at CR/rasterizer_impl.cu:328) rides along in the last kernel of the frame's depth sort
+template <int THREADS>
+__device__ __forceinline__ void zero_tile_ranges(uint2 *__restrict__ ranges, uint32_t T)
+{
+    if (ranges) for (uint32_t i = blockIdx.x * THREADS + threadIdx.x; i < T; i += gridDim.x * THREADS) ranges[i] = make_uint2(0u, 0u);
+}
+
 __global__ __launch_bounds__(256) void lds_rank_probe_kernel(uint32_t seed, int trials, int ndigits, uint32_t *__restrict__ bad)
 {
     __shared__ uint32_t cnt[4][256];
@@ -37,7 +110,7 @@ __global__ __launch_bounds__(256) void lds_rank_probe_kernel(uint32_t seed, int 
     uint32_t nb = 0;
     for (int t = 0; t < trials; t++) {
         for (int i = lane; i < 256; i += 64) cnt[wave][i] = 0;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
         x = x * 1664525u + 1013904223u;
         const uint32_t d = (x >> 16) % (uint32_t)ndigits;
         uint32_t expect = 0, same = 0;
@@ -57,43 +130,159 @@ __device__ __forceinline__ int to_int_sat(float f)
     return (int)f;
 }
 
+// ---------------------------------------------------------------- how a key becomes a digit
+// The histogram kernel and the partition kernel of the next section are written once, for a digit rule.  Three rules cover every sort:
+//   DigitBits<NBITS>   bits [shift, shift + nbits) of the key: the LSD depth sort's passes, both passes of the tile sort;
+//   DigitRange<BINS>   the top digit of the MSD depth sort, cut from the key range the frame's visible Gaussians occupy;
+//   DigitTable<BINS>   the bucket of the sample depth sort: a binary search of the splitter table, which the workgroup copies to LDS.
+// A rule is:
+//   Args             what the host passes;
+//   NBITS            the digit's width where the type fixes it (0: Args::nbits); width() returns it either way;
+//   KEEP             the partition holds an item's digit in a register between ranking and staging instead of deriving it twice;
+//   for_partition()  called by the whole workgroup at the top of the scatter kernel; ready() before the kernel's first digit;
+//   for_histogram()  called by the whole workgroup of the histogram kernel: it contains the workgroup barrier that publishes the zeroed
+//                    counters, and it calls load_keys() -- the kernel's own key loads -- at the point that suits the rule:
+//                      DigitBits   behind the barrier: nothing of the rule's to wait for, the loads go out last;
+//                      DigitRange  in front of the range reduction: the keys travel while the ranges are read and reduced;
+//                      DigitTable  behind its table loads: the LDS copy of the table waits for the table words alone, not for the
+//                                  keys (loads return in order), and the barrier then covers both;
+//   operator()       key -> digit.
+struct DigitBitsArgs { int shift, nbits; };
+template <int NBITS_> struct DigitBits {
+    typedef DigitBitsArgs Args;
+    static constexpr int NBITS = NBITS_;
+    static constexpr bool KEEP = false;
+    int shift, nbits; uint32_t mask;
+    static __device__ __forceinline__ DigitBits for_partition(const Args &a) { const int nb = NBITS > 0 ? NBITS : a.nbits; return { a.shift, nb, (1u << nb) - 1u }; }
+    template <class LOAD> static __device__ __forceinline__ DigitBits for_histogram(const Args &a, LOAD load_keys) { __syncthreads(); load_keys(); return for_partition(a); }
+    __device__ __forceinline__ int width() const { return nbits; }
+    __device__ __forceinline__ void ready() const {}
+    __device__ __forceinline__ uint32_t operator()(uint32_t key) const { return (key >> shift) & mask; }
+};
+
+// ---- top digit of the MSD depth sort (round 5).  The digit is cut from the key range the frame's visible Gaussians OCCUPY
+// (dparams = {kmin, shift, invisible key}: derived by the histogram kernel from the per-workgroup ranges the per-Gaussian kernel left):
+//   digit(key) = (key - kmin) >> shift  in [0, BINS - 2]   for a visible Gaussian,   BINS - 1 for the invisible key
+// -- cut from the static [min_depth, max_depth] a scene inside a narrow depth band landed in a handful of buckets.
+struct DlsParams { uint32_t kmin, shift, inv_key; };
+__device__ __forceinline__ DlsParams dls_params(const uint32_t *__restrict__ dparams) { return { dparams[0], dparams[1], dparams[2] }; }
+__device__ __forceinline__ uint32_t dls_digit(uint32_t key, const DlsParams &q, uint32_t bins) { return key == q.inv_key ? bins - 1u : (key - q.kmin) >> q.shift; }
+
+// Round 6: every workgroup of the histogram kernel derives dparams itself from the per-WORKGROUP key ranges the per-Gaussian kernel left
+// (P / 256 pairs = 31 KB at 1.0 M, from L2) -- the one-workgroup range kernel and its launch in front of the sort are gone; workgroup 0
+// leaves dparams in the frame flags for the partition and the bucket kernel.
+__device__ __forceinline__ DlsParams dls_reduce_ranges(const uint2 *__restrict__ ranges, uint32_t nranges, uint32_t inv_key, uint32_t bins, uint32_t *s_red /* 8 words */)
+{
+    uint32_t kmax = 0u, nkmin = 0u;
+    for (uint32_t base = 0; base < nranges; base += 8u * RS_THREADS) {          // 8 loads in flight per thread
+        uint2 p[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) { const uint32_t i = base + j * RS_THREADS + threadIdx.x; p[j] = i < nranges ? ranges[i] : make_uint2(0u, 0u); }
+#pragma unroll
+        for (int j = 0; j < 8; j++) { kmax = p[j].x > kmax ? p[j].x : kmax; nkmin = p[j].y > nkmin ? p[j].y : nkmin; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t a = __shfl_xor(kmax, o, 64), b = __shfl_xor(nkmin, o, 64);
+        kmax = a > kmax ? a : kmax; nkmin = b > nkmin ? b : nkmin;
+    }
+    if ((threadIdx.x & 63) == 0) { s_red[threadIdx.x >> 6] = kmax; s_red[4 + (threadIdx.x >> 6)] = nkmin; }
+    __syncthreads();
+    for (int w = 0; w < RS_THREADS / 64; w++) { kmax = s_red[w] > kmax ? s_red[w] : kmax; nkmin = s_red[4 + w] > nkmin ? s_red[4 + w] : nkmin; }
+    uint32_t kmin = ~nkmin, shift = 0;
+    if (kmax == 0u) kmin = 0u;           // no visible Gaussian at all
+    else {
+        const uint32_t range = kmax - kmin;
+        while ((range >> shift) > bins - 2u) shift++;
+    }
+    return { kmin, shift, inv_key };
+}
+template <int BINS> struct DigitRange {
+    static_assert(BINS == 512 || BINS == 1024, "bucket counts of the depth sorts");
+    struct Args { uint32_t *dparams; const uint2 *ranges; uint32_t nranges, inv_key; };       // (the partition reads dparams alone)
+    static constexpr int NBITS = BINS == 512 ? 9 : 10;
+    static constexpr bool KEEP = false;
+    DlsParams q;
+    template <class LOAD> static __device__ __forceinline__ DigitRange for_histogram(const Args &a, LOAD load_keys)
+    {
+        __shared__ uint32_t s_red[8];
+        load_keys();                                // (in flight under the reduction)
+        const DlsParams q = dls_reduce_ranges(a.ranges, a.nranges, a.inv_key, (uint32_t)BINS, s_red);
+        if (blockIdx.x == 0 && threadIdx.x == 0) { a.dparams[0] = q.kmin; a.dparams[1] = q.shift; a.dparams[2] = q.inv_key; a.dparams[3] = 0u; }
+        return { q };
+    }
+    static __device__ __forceinline__ DigitRange for_partition(const Args &a) { return { dls_params(a.dparams) }; }
+    __device__ __forceinline__ int width() const { return NBITS; }
+    __device__ __forceinline__ void ready() const {}
+    __device__ __forceinline__ uint32_t operator()(uint32_t key) const { return dls_digit(key, q, (uint32_t)BINS); }
+};
+
+// ---- bucket of the sample depth sort (ss_splitter_kernel below writes the table `ub`: upper bounds in the doubled key space, padded with ~0):
+// bucket(key) = number of entries below 2 key + 1
+template <int BINS>
+__device__ __forceinline__ uint32_t ss_bucket_of(const uint32_t *ub, uint32_t key)
+{
+    const uint32_t K = 2u * key + 1u;
+    uint32_t i = 0;
+#pragma unroll
+    for (uint32_t step = BINS / 2; step > 0; step >>= 1) if (ub[i + step - 1u] < K) i += step;      // (the last real entry is 2 inv + 1 >= K: i <= BINS - 1)
+    return i;
+}
+template <int BINS> struct DigitTable {
+    static_assert(BINS == 512 || BINS == 1024, "bucket counts of the depth sorts");
+    struct Args { const uint32_t *table; };
+    static constexpr int NBITS = BINS == 512 ? 9 : 10;
+    static constexpr bool KEEP = true;              // (a search of 9 or 10 dependent LDS reads)
+    static __device__ __forceinline__ uint32_t *lds() { __shared__ uint32_t ub[BINS]; return ub; }
+    static __device__ __forceinline__ DigitTable for_partition(const Args &a) { for (int b = threadIdx.x; b < BINS; b += RS_THREADS) lds()[b] = a.table[b]; return {}; }
+    template <class LOAD> static __device__ __forceinline__ DigitTable for_histogram(const Args &a, LOAD load_keys) { for_partition(a); load_keys(); __syncthreads(); return {}; }
+    __device__ __forceinline__ int width() const { return NBITS; }
+    __device__ __forceinline__ void ready() const { __syncthreads(); }            // the copy, before the first search
+    __device__ __forceinline__ uint32_t operator()(uint32_t key) const { return ss_bucket_of<BINS>(lds(), key); }
+};
+
 // ---------------------------------------------------------------- radix sort (8-bit digits, stable)
 // pass structure: histogram -> row scan -> scatter.  hist layout: [bin][block] followed by [bin] totals.
 // COPIES > 1: lane L counts into copy L % COPIES of the block's histogram (rows padded by one word, so the copies of a bin sit in
 // different LDS banks).  The tile sort's first pass sees long runs of equal digits -- the instances of one Gaussian are neighbouring
 // tiles, their high digit is the same -- and 64 lanes adding to ONE LDS word serialise (round 3: 14.7 us for a 30 MB read, the LDS
 // atomics of 7.5 M instances at one per cycle and CU); with 8 copies a run of 64 equal digits costs 8 serial steps, not 64.
-template <int ITEMS, int BINS, int COPIES>
-__global__ __launch_bounds__(RS_THREADS) void rs_histogram_kernel(const uint32_t *__restrict__ keys, uint32_t n, int shift,
-    uint32_t mask, uint32_t nblocks, uint32_t *__restrict__ hist, const uint32_t *__restrict__ n_dev)
+template <int ITEMS, int BINS, int COPIES, class DIGIT>
+__global__ __launch_bounds__(RS_THREADS) void rs_histogram_kernel(const uint32_t *__restrict__ keys, uint32_t n, uint32_t nblocks,
+    uint32_t *__restrict__ hist, const uint32_t *__restrict__ n_dev, typename DIGIT::Args da)
 {
     // n_dev (asynchronous forward, Ex4dParams.instance_capacity): the item count lives in device memory, `n` is the capacity the grid
     // was sized for; workgroups behind the last item write an all-zero column
     if (n_dev) { const uint32_t nd = *n_dev; n = nd < n ? nd : n; }
-    __shared__ uint32_t h_all[COPIES * (BINS + 1)];
-    uint32_t *h = h_all + (COPIES > 1 ? (threadIdx.x % COPIES) * (BINS + 1) : 0);
-    for (int b = threadIdx.x; b < COPIES * (BINS + 1); b += RS_THREADS) h_all[b] = 0;
-    __syncthreads();
+    constexpr int ROW = BINS + (COPIES > 1 ? 1 : 0);
+    __shared__ uint32_t h_all[COPIES * ROW];
+    uint32_t *h = h_all + (COPIES > 1 ? (threadIdx.x % COPIES) * ROW : 0);
+    for (int b = threadIdx.x; b < COPIES * ROW; b += RS_THREADS) h_all[b] = 0;
     const uint32_t base = blockIdx.x * (RS_THREADS * ITEMS);
-    if (base < n) {              // (uniform)
-        // all loads in flight before the first LDS atomic (clamped index instead of a branch per load)
-        uint32_t k[ITEMS];
+    // all loads in flight before the first LDS atomic (clamped index instead of a branch per load); the rule says where they go
+    // between its own loads and its barrier, which publishes h = 0
+    uint32_t k[ITEMS];
+    const DIGIT dg = DIGIT::for_histogram(da, [&]() {
+        if (base < n) {              // (uniform)
 #pragma unroll
-        for (int it = 0; it < ITEMS; it++) {
-            const uint32_t i = base + it * RS_THREADS + threadIdx.x;
-            k[it] = keys[i < n ? i : n - 1];
+            for (int it = 0; it < ITEMS; it++) {
+                const uint32_t i = base + it * RS_THREADS + threadIdx.x;
+                k[it] = keys[i < n ? i : n - 1];
+            }
         }
+    });
+    if (base < n) {
 #pragma unroll
         for (int it = 0; it < ITEMS; it++) {
             const uint32_t i = base + it * RS_THREADS + threadIdx.x;
-            if (i < n) atomicAdd(&h[(k[it] >> shift) & mask], 1u);
+            if (i < n) atomicAdd(&h[dg(k[it])], 1u);
         }
     }
     __syncthreads();
     for (int b = threadIdx.x; b < BINS; b += RS_THREADS) {
         uint32_t c = 0;
 #pragma unroll
-        for (int k = 0; k < COPIES; k++) c += h_all[k * (BINS + 1) + b];
+        for (int k = 0; k < COPIES; k++) c += h_all[k * ROW + b];
         hist[(size_t)b * nblocks + blockIdx.x] = c;
     }
 }
@@ -144,77 +333,10 @@ __global__ __launch_bounds__(256) void rs_scan_rows_kernel(uint32_t nblocks, uin
     if (threadIdx.x == 0) hist[(size_t)bins * nblocks + blockIdx.x] = carry_s;
 }
 
-// ---- top digit of the MSD depth sort (round 5).  The digit is cut from the key range the frame's visible Gaussians OCCUPY
-// (dparams = {kmin, shift, invisible key}: derived by dls_range_kernel from the per-wave ranges the per-Gaussian kernel left):
-//   digit(key) = (key - kmin) >> shift  in [0, BINS - 2]   for a visible Gaussian,   BINS - 1 for the invisible key
-// -- cut from the static [min_depth, max_depth] a scene inside a narrow depth band landed in a handful of buckets.
-struct DlsParams { uint32_t kmin, shift, inv_key; };
-__device__ __forceinline__ DlsParams dls_params(const uint32_t *__restrict__ dparams) { return { dparams[0], dparams[1], dparams[2] }; }
-__device__ __forceinline__ uint32_t dls_digit(uint32_t key, const DlsParams &q, uint32_t bins) { return key == q.inv_key ? bins - 1u : (key - q.kmin) >> q.shift; }
-
-// Round 6: every workgroup of the histogram kernel derives dparams itself from the per-WORKGROUP key ranges the per-Gaussian kernel left
-// (P / 256 pairs = 31 KB at 1.0 M, from L2) -- the one-workgroup range kernel and its launch in front of the sort are gone; workgroup 0
-// leaves dparams in the frame flags for the partition and the bucket kernel.
-__device__ __forceinline__ DlsParams dls_reduce_ranges(const uint2 *__restrict__ ranges, uint32_t nranges, uint32_t inv_key, uint32_t bins, uint32_t *s_red /* 8 words */)
-{
-    uint32_t kmax = 0u, nkmin = 0u;
-    for (uint32_t base = 0; base < nranges; base += 8u * RS_THREADS) {          // 8 loads in flight per thread
-        uint2 p[8];
-#pragma unroll
-        for (int j = 0; j < 8; j++) { const uint32_t i = base + j * RS_THREADS + threadIdx.x; p[j] = i < nranges ? ranges[i] : make_uint2(0u, 0u); }
-#pragma unroll
-        for (int j = 0; j < 8; j++) { kmax = p[j].x > kmax ? p[j].x : kmax; nkmin = p[j].y > nkmin ? p[j].y : nkmin; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t a = __shfl_xor(kmax, o, 64), b = __shfl_xor(nkmin, o, 64);
-        kmax = a > kmax ? a : kmax; nkmin = b > nkmin ? b : nkmin;
-    }
-    if ((threadIdx.x & 63) == 0) { s_red[threadIdx.x >> 6] = kmax; s_red[4 + (threadIdx.x >> 6)] = nkmin; }
-    __syncthreads();
-    for (int w = 0; w < RS_THREADS / 64; w++) { kmax = s_red[w] > kmax ? s_red[w] : kmax; nkmin = s_red[4 + w] > nkmin ? s_red[4 + w] : nkmin; }
-    uint32_t kmin = ~nkmin, shift = 0;
-    if (kmax == 0u) kmin = 0u;           // no visible Gaussian at all
-    else {
-        const uint32_t range = kmax - kmin;
-        while ((range >> shift) > bins - 2u) shift++;
-    }
-    return { kmin, shift, inv_key };
-}
-
-template <int ITEMS, int BINS>
-__global__ __launch_bounds__(RS_THREADS) void dls_histogram_kernel(const uint32_t *__restrict__ keys, uint32_t n, uint32_t nblocks,
-    uint32_t *__restrict__ hist, uint32_t *__restrict__ dparams, const uint2 *__restrict__ ranges, uint32_t nranges, uint32_t inv_key)
-{
-    __shared__ uint32_t h[BINS];
-    __shared__ uint32_t s_red[8];
-    for (int b = threadIdx.x; b < BINS; b += RS_THREADS) h[b] = 0;
-    const uint32_t base = blockIdx.x * (RS_THREADS * ITEMS);
-    uint32_t k[ITEMS];
-    if (base < n) {
-#pragma unroll
-        for (int it = 0; it < ITEMS; it++) {
-            const uint32_t i = base + it * RS_THREADS + threadIdx.x;
-            k[it] = keys[i < n ? i : n - 1];
-        }
-    }
-    const DlsParams q = dls_reduce_ranges(ranges, nranges, inv_key, (uint32_t)BINS, s_red);      // (its barrier publishes h = 0)
-    if (blockIdx.x == 0 && threadIdx.x == 0) { dparams[0] = q.kmin; dparams[1] = q.shift; dparams[2] = q.inv_key; dparams[3] = 0u; }
-    if (base < n) {
-#pragma unroll
-        for (int it = 0; it < ITEMS; it++) {
-            const uint32_t i = base + it * RS_THREADS + threadIdx.x;
-            if (i < n) atomicAdd(&h[dls_digit(k[it], q, BINS)], 1u);
-        }
-    }
-    __syncthreads();
-    for (int b = threadIdx.x; b < BINS; b += RS_THREADS) hist[(size_t)b * nblocks + blockIdx.x] = h[b];
-}
-
 // Scatter pass.  A block owns RS_CHUNK consecutive items; wave w owns the w-th quarter of them and walks it in
 // rounds of 64 consecutive items, so the stable order inside the block is (wave, round, lane).
-//  phase 1  each wave ranks its items against its own running per-digit counters (wave-private LDS, wave64
-//           ballot match, no block barrier);
+//  phase 1  each wave ranks its items against its own running per-digit counters (wave-private LDS, wave_rank:
+//           wave64 ballot match or LDS atomics, no block barrier);
 //  phase 2  one barrier: per digit, exclusive scan over the 4 waves + block-local digit starts + global bases;
 //  phase 3  items go to their block-local sorted slot in LDS, one barrier, then the block streams the staged
 //           chunk out: neighbouring threads write neighbouring addresses of the same digit run (coalesced).
@@ -223,7 +345,8 @@ __global__ __launch_bounds__(RS_THREADS) void dls_histogram_kernel(const uint32_
 // MODE 2: packed words in (digit = word >> shift), values out; the workgroup's item range and bucket come from the block table, its
 //         global digit starts from the bucket's span of the row-scanned histogram; also writes the tile ranges (pass B).
 // MODE 3: (key, value, packed rect) triples in, triples out, and workgroup 0 leaves the first output position of every digit in
-//         `bucket_starts` (the MSD partition of the depth sort, below: depth_local_sort_kernel finishes every bucket in LDS).
+//         `bucket_starts` (the partition of the MSD and of the sample depth sort, below: a bucket kernel finishes every bucket in LDS).
+// DIGIT:  how a key becomes a digit (above).  MODE 0 .. 2 run with DigitBits, MODE 3 with DigitRange or DigitTable.
 // Pass B of the tile sort cuts every bucket (= high digit) into blocks of <= 4096 items, so that no block straddles two buckets.
 // Every workgroup derives its own block from the <= 256 bucket totals of pass A (two scans + a 8-step search: cheaper than a
 // one-workgroup table kernel and its launch in the middle of the sort):
@@ -265,16 +388,13 @@ __device__ __forceinline__ TsBlock ts_locate_block(const uint32_t *__restrict__ 
     }
     return t;
 }
-// NBITS > 0: digit width known at compile time -- the match loop below unrolls (5 VALU per bit instead of a 12-slot loop body with
-// its scalar bookkeeping); 0 = any width at run time.
-template <int ITEMS, int BINS, int MODE, int NBITS>
+template <int ITEMS, int BINS, int MODE, class DIGIT>
 __global__ __launch_bounds__(RS_THREADS) void rs_scatter_kernel(const uint32_t *__restrict__ keys_in,
     const uint32_t *__restrict__ vals_in, uint32_t *__restrict__ keys_out, uint32_t *__restrict__ vals_out,
-    uint32_t n, int shift, int nbits, uint32_t nblocks, const uint32_t *__restrict__ hist,
+    uint32_t n, typename DIGIT::Args da, uint32_t nblocks, const uint32_t *__restrict__ hist,
     int low_bits, const uint32_t *__restrict__ bucket_totals, int nbuckets, uint2 *__restrict__ ranges, const uint32_t *__restrict__ n_dev,
     const uint32_t *__restrict__ rects_in = nullptr, uint32_t *__restrict__ rects_out = nullptr, uint32_t *__restrict__ bucket_starts = nullptr,
-    const uint32_t *__restrict__ dparams = nullptr, uint32_t range_stride = 0, uint32_t out_cap = 0xFFFFFFFFu,
-    const Ex4dTsBlock *__restrict__ block_table = nullptr)
+    uint32_t range_stride = 0, uint32_t out_cap = 0xFFFFFFFFu, const Ex4dTsBlock *__restrict__ block_table = nullptr)
 {
     // MODE 2 only: range_stride = tile ids per bucket (0: 1 << nbits, the binary split of the pair sort; the row-segment sort of round 6
     // has bucket = tile row, digit = tile column: the image's tiles per row); out_cap = capacity of the packed / output arrays (an
@@ -282,7 +402,7 @@ __global__ __launch_bounds__(RS_THREADS) void rs_scatter_kernel(const uint32_t *
     if (n_dev) { const uint32_t nd = *n_dev; n = nd < n ? nd : n; }      // (see rs_histogram_kernel)
     // MODE 0, last pass of the LSD depth sort in front of the row-segment tile sort (round 6): the zero-fill of the tile ranges rides along
     // (range_stride = number of tiles), and the write-out below gathers every item's packed rect by its value (rects_in -> rects_out)
-    if (MODE == 0 && ranges) for (uint32_t i = blockIdx.x * RS_THREADS + threadIdx.x; i < range_stride; i += gridDim.x * RS_THREADS) ranges[i] = make_uint2(0u, 0u);
+    if (MODE == 0) zero_tile_ranges<RS_THREADS>(ranges, range_stride);
     if (MODE != 2 && blockIdx.x * (uint32_t)(RS_THREADS * ITEMS) >= n) return;      // behind the last item (uniform: the whole workgroup)
     __shared__ uint32_t wave_cnt[4][BINS];        // per-wave digit counts -> exclusive block-local offsets
     __shared__ uint32_t local_start[BINS];        // first block-local slot of each digit
@@ -300,17 +420,11 @@ __global__ __launch_bounds__(RS_THREADS) void rs_scatter_kernel(const uint32_t *
     static_assert(sizeof(uint32_t) * (4 * BINS + 2 * BINS + 8) + sizeof(uint32_t) * STAGE_WORDS + sizeof(uint32_t) * (MODE == 3 ? RS_THREADS * ITEMS : 1) <= 80 * 1024,
                   "rs_scatter_kernel: static LDS beyond 80 KB (two workgroups per CU)");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (NBITS > 0) nbits = NBITS;
-    const uint32_t mask = (1u << nbits) - 1u;
+    const DIGIT digit_of = DIGIT::for_partition(da);
+    const int nbits = digit_of.width();
     const int nbins = 1 << nbits;
-    // MODE 3: the digit of the MSD depth sort (dls_digit); every other mode: bits [shift, shift + nbits) of the key
-    DlsParams dq = { 0u, 0u, 0u };
-    if (MODE == 3) dq = dls_params(dparams);
-    auto digit_of = [&](uint32_t k) -> uint32_t { return MODE == 3 ? dls_digit(k, dq, (uint32_t)BINS) : ((k >> shift) & mask); };
     for (int i = lane; i < BINS; i += 64) wave_cnt[wave][i] = 0;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sync();
 
     const bool lds_rank = ex4d_g_rank_lds != 0;          // (uniform)
     constexpr uint32_t CHUNK = RS_THREADS * ITEMS;
@@ -329,7 +443,6 @@ __global__ __launch_bounds__(RS_THREADS) void rs_scatter_kernel(const uint32_t *
         if (block_end > out_cap) block_end = out_cap;
     }
     const uint32_t base = block_first + wave * (CHUNK / 4);
-    const uint64_t lt = (1ull << lane) - 1ull;
     // (round 6) the histogram words this thread's digits need behind the ranking -- the block's own prefix, the digit totals / the bucket's
     // span of the row-scanned histogram -- are requested HERE, in front of the items: their round trip (scattered 4-byte loads) hides behind
     // the load + ranking phase instead of standing between two barriers of the workgroup's critical path
@@ -348,7 +461,7 @@ __global__ __launch_bounds__(RS_THREADS) void rs_scatter_kernel(const uint32_t *
         }
         pre_hb[k] = live ? hist[(size_t)d * nblocks + blockIdx.x] : 0u;
     }
-    uint32_t key[ITEMS], val[ITEMS], pos[ITEMS], rct[MODE == 3 ? ITEMS : 1];
+    uint32_t key[ITEMS], val[ITEMS], pos[ITEMS], rct[MODE == 3 ? ITEMS : 1], dig[DIGIT::KEEP ? ITEMS : 1];
 #pragma unroll
     for (int it = 0; it < ITEMS; it++) {
         // unconditional loads from a clamped index (no exec-masked branch per item): the waits before the first ranking steps
@@ -359,50 +472,14 @@ __global__ __launch_bounds__(RS_THREADS) void rs_scatter_kernel(const uint32_t *
         val[it] = (MODE == 2) ? 0u : (vals_in ? vals_in[ic] : ic);        // vals_in == nullptr: the values are the item indices (first pass of the depth sort)
         if constexpr (MODE == 3) rct[it] = rects_in[ic];
     }
+    digit_of.ready();
 #pragma unroll
     for (int it = 0; it < ITEMS; it++) {
         const uint32_t i = base + it * 64 + lane;
         const bool valid = i < block_end;
         const uint32_t d = digit_of(key[it]);
-        if (lds_rank) {
-            // stable rank by the LDS atomic's return value (round 6; see ex4d_g_rank_lds above): index among this wave's items of digit d
-            pos[it] = valid ? atomicAdd(&wave_cnt[wave][d], 1u) : 0u;
-            continue;
-        }
-        // lanes holding the same digit: per bit keep the ballot if my bit is set, its complement otherwise -- written as
-        // ballot ^ (bit - 1) on 32-bit halves (plain xor/and; a select here compiles to the VOP2 v_cndmask that issues in ~24
-        // cycles on gfx950 and made this loop the most expensive part of the pass)
-        const uint64_t vmask = __builtin_amdgcn_ballot_w64(valid);
-        uint32_t plo = (uint32_t)vmask, phi = (uint32_t)(vmask >> 32);
-        if (NBITS > 0) {
-#pragma unroll
-            for (int b = 0; b < NBITS; b++) {
-                const uint64_t bal = __builtin_amdgcn_ballot_w64((d & (1u << b)) != 0u);
-                uint32_t flip;                                    // 0 when my bit is set, ~0 otherwise: my bit IS my lane's bit of the ballot
-                asm("v_cndmask_b32_e64 %0, -1, 0, %1" : "=v"(flip) : "s"(bal));
-                plo &= (uint32_t)bal ^ flip;
-                phi &= (uint32_t)(bal >> 32) ^ flip;
-            }
-        } else {
-            for (int b = 0; b < nbits; b++) {
-                const uint32_t bit = (d >> b) & 1u;
-                const uint64_t bal = __builtin_amdgcn_ballot_w64(bit != 0u);
-                const uint32_t flip = bit - 1u;                   // 0 when my bit is set, ~0 otherwise
-                plo &= (uint32_t)bal ^ flip;
-                phi &= (uint32_t)(bal >> 32) ^ flip;
-            }
-        }
-        const uint64_t peers = ((uint64_t)phi << 32) | plo;
-        const uint32_t rank = __popcll(peers & lt);
-        // every lane reads its digit's counter (the peers of a digit read ONE word: an LDS broadcast), then the first lane of every
-        // digit adds the digit's count -- a wave's LDS accesses execute in order, so the reads see the value before the update
-        // (round 5; rounds 1-4: the leader read, wrote and handed `before` to its peers through ds_bpermute: one more LDS round trip)
-        const uint32_t before = wave_cnt[wave][valid ? d : 0u];
-        if (valid && rank == 0) wave_cnt[wave][d] = before + (uint32_t)__popcll(peers);      // one lane per distinct digit: no two writers share an address
-        pos[it] = before + rank;                  // index among this wave's items of digit d
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        if (DIGIT::KEEP) dig[it] = d;
+        pos[it] = wave_rank<DIGIT::NBITS>(wave_cnt[wave], d, nbits, valid, lds_rank);      // index among this wave's items of digit d
     }
     __syncthreads();
     {
@@ -463,7 +540,7 @@ __global__ __launch_bounds__(RS_THREADS) void rs_scatter_kernel(const uint32_t *
     for (int it = 0; it < ITEMS; it++) {
         const uint32_t i = base + it * 64 + lane;
         if (i < block_end) {
-            const uint32_t d = digit_of(key[it]);
+            const uint32_t d = DIGIT::KEEP ? dig[it] : digit_of(key[it]);
             if constexpr (MODE == 2) stage_w[wave_cnt[wave][d] + pos[it]] = key[it];
             else stage[wave_cnt[wave][d] + pos[it]] = make_uint2(key[it], val[it]);
             if constexpr (MODE == 3) stage_r[wave_cnt[wave][d] + pos[it]] = rct[it];
@@ -528,12 +605,12 @@ __global__ __launch_bounds__(RS_THREADS) void ts_histogram_kernel(const uint32_t
 // ---------------------------------------------------------------- depth sort, MSD first: every bucket finished in LDS
 // Round 5.  The LSD depth sort was nine launches (3 x histogram / row scan / scatter) of 5-13 us each, bound by launch ramp and
 // latency, not by its 8 MB.  Now: ONE global partition of the P (key, id, packed rect) triples by the TOP DLS_MSD_BITS bits of the
-// depth key (histogram -> row scan -> scatter, MODE 3 above; stable, so equal keys keep ascending ids) -- a bucket then holds
+// depth key (histogram -> row scan -> scatter: MODE 3 above with DigitRange; stable, so equal keys keep ascending ids) -- a bucket then holds
 // ~1.5 k Gaussians at 1.0 M -- and ONE kernel in which a workgroup per bucket sorts its bucket on the remaining `rem` key bits
 // entirely in LDS and permutes (id, rect) IN PLACE: the depth order and the rects in depth order (which the tile scan used to
 // gather at random: 52 MB of traffic for a 4 MB array) fall out of the same kernel.  4 launches instead of 9 + a streaming scan.
 //   * LDS word = (key & remmask) << 13 | arrival index: sorting the words by their key bits with a STABLE LSD radix sort (9-bit digits,
-//     wave-private ballot ranking like the scatter kernel) is the stable sort by key; the payload is fetched once at the end through the
+//     wave_rank like the scatter kernel) is the stable sort by key; the payload is fetched once at the end through the
 //     arrival index (a gather inside the bucket's own 8-32 KB window).
 //   * invisible Gaussians carry a key whose top digit is theirs alone (host: one past the digit of max_depth): the partition
 //     leaves them in id order behind every visible bucket with their zero rect; nobody touches that bucket again.
@@ -549,53 +626,6 @@ template <int THREADS> struct DlsLds {
 };
 #define DLS_IDX_BITS 13      // (the widest arrival index: what the host checks the key bits against)
 
-__device__ __forceinline__ void dls_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-// lanes of the wave that hold the same digit as this lane (among the valid ones); invalid lanes get 0.
-// NBITS > 0: digit width known at compile time (unrolled, 5 VALU per bit: see rs_scatter_kernel); 0: `nbits` at run time
-template <int NBITS>
-__device__ __forceinline__ uint64_t dls_peers(uint32_t d, int nbits, bool valid)
-{
-    const uint64_t vmask = __builtin_amdgcn_ballot_w64(valid);
-    uint32_t plo = (uint32_t)vmask, phi = (uint32_t)(vmask >> 32);
-    if (NBITS > 0) {
-#pragma unroll
-        for (int b = 0; b < NBITS; b++) {
-            const uint64_t bal = __builtin_amdgcn_ballot_w64((d & (1u << b)) != 0u);
-            uint32_t flip;                                    // 0 when my bit is set, ~0 otherwise: my bit IS my lane's bit of the ballot
-            asm("v_cndmask_b32_e64 %0, -1, 0, %1" : "=v"(flip) : "s"(bal));
-            plo &= (uint32_t)bal ^ flip;
-            phi &= (uint32_t)(bal >> 32) ^ flip;
-        }
-    } else {
-        for (int b = 0; b < nbits; b++) {
-            const uint32_t bit = (d >> b) & 1u;
-            const uint64_t bal = __builtin_amdgcn_ballot_w64(bit != 0u);
-            const uint32_t flip = bit - 1u;                   // 0 when my bit is set, ~0 otherwise
-            plo &= (uint32_t)bal ^ flip;
-            phi &= (uint32_t)(bal >> 32) ^ flip;
-        }
-    }
-    const uint64_t peers = ((uint64_t)phi << 32) | plo;
-    return valid ? peers : 0ull;
-}
-// stable rank of this lane's item among the wave's items processed so far: returns the index among the wave's items of digit d
-// (wave-private counter row `cnt`), and bumps the counter.  All 64 lanes call it.
-template <int NBITS>
-__device__ __forceinline__ uint32_t dls_rank(uint32_t *cnt, uint32_t d, int nbits, bool valid, int lane)
-{
-    if (ex4d_g_rank_lds != 0) return valid ? atomicAdd(&cnt[d], 1u) : 0u;      // (uniform; round 6: see ex4d_g_rank_lds)
-    const uint64_t peers = dls_peers<NBITS>(d, nbits, valid);
-    const uint32_t rank = __popcll(peers & ((1ull << lane) - 1ull));
-    const uint32_t before = cnt[valid ? d : 0u];                            // (all peers read one word; see rs_scatter_kernel)
-    if (valid && rank == 0) cnt[d] = before + (uint32_t)__popcll(peers);    // one lane per distinct digit
-    dls_wave_sync();
-    return before + rank;
-}
 // cnt[w][d] (counts of digit d among wave w's items) -> first destination slot of (d, w): exclusive scan over (digit, wave)
 template <int THREADS>
 __device__ __forceinline__ void dls_scan_counts(DlsLds<THREADS> &L, int nbits)
@@ -627,6 +657,8 @@ __device__ __forceinline__ void dls_scan_counts(DlsLds<THREADS> &L, int nbits)
     }
     __syncthreads();
 }
+// a bucket's `rem` key bits are sorted in dls_passes(rem) LSD passes of at most 9 bits, as even as they come
+__device__ __forceinline__ int dls_passes(int rem) { return (rem + 8) / 9; }
 __device__ __forceinline__ int dls_pass_bits(int rem, int lo, int npass, int pass) { return (rem - lo + (npass - pass) - 1) / (npass - pass); }
 
 // n > cap: the workgroup sorts the bucket's (key, id, rect) triples through global memory; X = the partition's output slice (where the
@@ -637,7 +669,8 @@ __device__ __forceinline__ void dls_sort_through_memory(DlsLds<THREADS> &L, uint
 {
     constexpr int DLS_WAVES = THREADS / 64, DLS_THREADS = THREADS;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int npass = (rem + 8) / 9;
+    const int npass = dls_passes(rem);
+    const bool lds_rank = ex4d_g_rank_lds != 0;
     const uint32_t m = ((n + DLS_WAVES * 64 - 1) / (DLS_WAVES * 64)) * 64;          // items per wave (a multiple of 64)
     const uint32_t wbase = wave * m < n ? wave * m : n, wend = (wbase + m) < n ? (wbase + m) : n;
     uint32_t *sk = xk, *sv = xv, *sr = xr, *dk = yk, *dv = yv, *dr = yr;
@@ -645,7 +678,7 @@ __device__ __forceinline__ void dls_sort_through_memory(DlsLds<THREADS> &L, uint
         const int nbits = dls_pass_bits(rem, lo, npass, pass);
         const uint32_t mask = (1u << nbits) - 1u;
         for (int i = lane; i < 512; i += 64) L.cnt[wave][i] = 0;
-        dls_wave_sync();
+        wave_sync();
         for (uint32_t i = wbase + lane; i < wend; i += 64) atomicAdd(&L.cnt[wave][((sk[i] - kmin) >> lo) & mask], 1u);
         __syncthreads();
         dls_scan_counts(L, nbits);
@@ -654,7 +687,7 @@ __device__ __forceinline__ void dls_sort_through_memory(DlsLds<THREADS> &L, uint
             const bool valid = i < wend;
             const uint32_t k = valid ? sk[i] : 0u, v = valid ? sv[i] : 0u, r = valid ? sr[i] : 0u;
             const uint32_t d = ((k - kmin) >> lo) & mask;
-            const uint32_t dst = dls_rank<0>(L.cnt[wave], d, nbits, valid, lane);
+            const uint32_t dst = wave_rank<0>(L.cnt[wave], d, nbits, valid, lds_rank);
             if (valid) { dk[dst] = k; dv[dst] = v; dr[dst] = r; }
         }
         __threadfence();
@@ -715,25 +748,28 @@ __device__ __forceinline__ uint32_t dls_scan_from_memory(DlsLds<THREADS> &L, con
     return carry;
 }
 
-// one stable LSD pass over the n words in L.buf on the digit (word >> sh) & (2^nbits - 1): wave w owns the w-th run of m words
+// one stable LSD pass over the n words in L.buf on the digit (word >> sh) & (2^nbits - 1): wave w owns the w-th run of m words.
+// idx16 (LDS, optional: the pair path of the sample sort): idx16[i] travels with word i
 template <int THREADS, int NBITS>
-__device__ __forceinline__ void dls_lds_pass(DlsLds<THREADS> &L, uint32_t n, uint32_t m, int sh, int nbits)
+__device__ __forceinline__ void dls_lds_pass(DlsLds<THREADS> &L, uint32_t n, uint32_t m, int sh, int nbits, uint16_t *idx16 = nullptr)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (NBITS > 0) nbits = NBITS;
     const uint32_t mask = (1u << nbits) - 1u;
     const uint32_t wbase = wave * m;
+    const bool lds_rank = ex4d_g_rank_lds != 0;          // (uniform)
     for (int i = lane; i < (1 << nbits); i += 64) L.cnt[wave][i] = 0;
-    dls_wave_sync();
-    uint32_t word[DLS_ITEMS], pos[DLS_ITEMS];
+    wave_sync();
+    uint32_t word[DLS_ITEMS], pos[DLS_ITEMS], idx[DLS_ITEMS];
 #pragma unroll
     for (int it = 0; it < DLS_ITEMS; it++) {
-        word[it] = 0u; pos[it] = 0u;
+        word[it] = 0u; pos[it] = 0u; idx[it] = 0u;
         if ((uint32_t)(it * 64) < m) {                    // (wave-uniform)
             const uint32_t i = wbase + it * 64 + lane;
             const bool valid = i < n;
             word[it] = valid ? L.buf[i] : 0u;
-            pos[it] = dls_rank<NBITS>(L.cnt[wave], (word[it] >> sh) & mask, nbits, valid, lane);
+            if (idx16) idx[it] = valid ? idx16[i] : 0u;
+            pos[it] = wave_rank<NBITS>(L.cnt[wave], (word[it] >> sh) & mask, nbits, valid, lds_rank);
         }
     }
     __syncthreads();                   // every word is in a register, every count final
@@ -742,10 +778,64 @@ __device__ __forceinline__ void dls_lds_pass(DlsLds<THREADS> &L, uint32_t n, uin
     for (int it = 0; it < DLS_ITEMS; it++) {
         if ((uint32_t)(it * 64) < m) {
             const uint32_t i = wbase + it * 64 + lane;
-            if (i < n) L.buf[L.cnt[wave][(word[it] >> sh) & mask] + pos[it]] = word[it];
+            if (i < n) { const uint32_t dst = L.cnt[wave][(word[it] >> sh) & mask] + pos[it]; L.buf[dst] = word[it]; if (idx16) idx16[dst] = (uint16_t)idx[it]; }
         }
     }
     __syncthreads();
+}
+
+// ---- what the bucket kernels share (depth_local_sort_kernel here; ss_bucket_kernel and, for the passes, ss_splitter_kernel below)
+// the bucket's n <= CAP keys as LDS words: L.buf[p] = ((keys[p] - kbase) & (2^rem - 1)) << IDX_BITS | p (p: the arrival index)
+template <int THREADS>
+__device__ __forceinline__ void dls_load_packed(DlsLds<THREADS> &L, const uint32_t *keys, uint32_t n, uint32_t kbase, int rem)
+{
+    const uint32_t remmask = (1u << rem) - 1u;
+    uint32_t k[DLS_ITEMS];                           // every load in flight before the first LDS store
+#pragma unroll
+    for (int j = 0; j < DLS_ITEMS; j++) { const uint32_t p = threadIdx.x + j * THREADS; k[j] = p < n ? keys[p] : 0u; }
+#pragma unroll
+    for (int j = 0; j < DLS_ITEMS; j++) { const uint32_t p = threadIdx.x + j * THREADS; if (p < n) L.buf[p] = (((k[j] - kbase) & remmask) << DlsLds<THREADS>::IDX_BITS) | p; }
+    __syncthreads();
+}
+// the stable LSD sort of the n words in L.buf on their bits [sh, sh + rem).  SPLITS: the digit widths of the MSD sort's common key ranges
+// at compile time (rem = 16: depths in (4, 300]; 17: (0.01, 300]), any other at run time.  The sample sort's buckets have whatever span
+// their splitters leave: its kernels take the run-time passes alone (with the two unrolled passes compiled in and never taken,
+// ss_bucket_kernel<512> ran 0.7 us longer at 1.0 M Gaussians)
+template <int THREADS, bool SPLITS>
+__device__ __forceinline__ void dls_sort_words(DlsLds<THREADS> &L, uint32_t n, int sh, int rem)
+{
+    const uint32_t m = ((n + THREADS - 1) / THREADS) * 64;          // items per wave: a multiple of 64, <= 1024
+    if constexpr (SPLITS) {
+        if (rem == 16) { dls_lds_pass<THREADS, 8>(L, n, m, sh, 8); dls_lds_pass<THREADS, 8>(L, n, m, sh + 8, 8); return; }
+        else if (rem == 17) { dls_lds_pass<THREADS, 9>(L, n, m, sh, 9); dls_lds_pass<THREADS, 8>(L, n, m, sh + 9, 8); return; }
+    }
+    const int npass = dls_passes(rem);
+    for (int pass = 0, lo = 0; pass < npass; pass++) {
+        const int nbits = dls_pass_bits(rem, lo, npass, pass);
+        dls_lds_pass<THREADS, 0>(L, n, m, sh + lo, nbits);
+        lo += nbits;
+    }
+}
+// payload of the bucket at [s, s + n): position p takes the (id, rect) that arrived at index idx_of(p).  In place: every load lands before
+// any store goes out.  (vb[s + p], not (vb + s)[p]: the 32-bit sum keeps the kernel inside its register budget.)
+// counts: L.buf[p] = tiles of the rect that landed at p (for the fused tile scan)
+template <int THREADS, class IDX>
+__device__ __forceinline__ void dls_permute_payload(DlsLds<THREADS> &L, uint32_t *vb, uint32_t *rb, uint32_t s, uint32_t n, IDX idx_of, bool counts)
+{
+    uint32_t v[DLS_ITEMS], r[DLS_ITEMS];
+#pragma unroll
+    for (int j = 0; j < DLS_ITEMS; j++) {
+        const uint32_t p = threadIdx.x + j * THREADS;
+        v[j] = 0u; r[j] = 0u;
+        if (p < n) { const uint32_t idx = idx_of(p); v[j] = vb[s + idx]; r[j] = rb[s + idx]; }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < DLS_ITEMS; j++) {
+        const uint32_t p = threadIdx.x + j * THREADS;
+        if (p < n) { vb[s + p] = v[j]; rb[s + p] = r[j]; if (counts) L.buf[p] = rect4_count(r[j]); }
+    }
 }
 
 // THREADS = 256: buckets of <= 4096 in LDS, 24 KB of LDS (the choice up to ~1.2 M Gaussians: ~1.5 k per bucket, every workgroup of the
@@ -755,12 +845,11 @@ __global__ __launch_bounds__(THREADS, THREADS == 512 ? 4 : 5) void depth_local_s
     const uint32_t *__restrict__ starts, const uint32_t *__restrict__ totals, const uint32_t *__restrict__ dparams, uint32_t cap,
     uint32_t *__restrict__ local_incl, uint32_t *__restrict__ bucket_sums, int T, uint2 *__restrict__ ranges, uint32_t *__restrict__ watch)
 {
-    constexpr int DLS_THREADS = THREADS, DLS_WAVES = THREADS / 64, DLS_CAP = THREADS * DLS_ITEMS, IDX_BITS = DlsLds<THREADS>::IDX_BITS;
+    constexpr int DLS_THREADS = THREADS, DLS_CAP = THREADS * DLS_ITEMS, IDX_BITS = DlsLds<THREADS>::IDX_BITS;
     __shared__ DlsLds<THREADS> L;
     const uint32_t b = blockIdx.x;
     const int tid = threadIdx.x;
-    // the zero-fill of the tile ranges (cudaMemset at CR/rasterizer_impl.cu:328) rides along here (it used to ride in the tile scan)
-    if (ranges) for (int i = b * DLS_THREADS + tid; i < T; i += gridDim.x * DLS_THREADS) ranges[i] = make_uint2(0u, 0u);
+    zero_tile_ranges<THREADS>(ranges, (uint32_t)T);
     const uint32_t n = totals[b], s = starts[b];
     const DlsParams dq = dls_params(dparams);
     const int rem = (int)dq.shift;                        // key bits below the top digit: what is left to sort inside a bucket
@@ -785,42 +874,9 @@ __global__ __launch_bounds__(THREADS, THREADS == 512 ? 4 : 5) void depth_local_s
         }
         return;
     }
-    const uint32_t remmask = (1u << rem) - 1u;
-    {
-        uint32_t k[DLS_ITEMS];                           // every load in flight before the first LDS store
-#pragma unroll
-        for (int j = 0; j < DLS_ITEMS; j++) { const uint32_t p = tid + j * DLS_THREADS; k[j] = p < n ? kb[s + p] : 0u; }
-#pragma unroll
-        for (int j = 0; j < DLS_ITEMS; j++) { const uint32_t p = tid + j * DLS_THREADS; if (p < n) L.buf[p] = (((k[j] - dq.kmin) & remmask) << IDX_BITS) | p; }
-    }
-    __syncthreads();
-    const int npass = (rem + 8) / 9;
-    const uint32_t m = ((n + DLS_WAVES * 64 - 1) / (DLS_WAVES * 64)) * 64;          // items per wave: a multiple of 64, <= 1024
-    // digit widths of the common key ranges at compile time (rem = 16: depths in (4, 300]; 17: (0.01, 300]), any other at run time
-    if (rem == 16) { dls_lds_pass<THREADS, 8>(L, n, m, IDX_BITS, 8); dls_lds_pass<THREADS, 8>(L, n, m, IDX_BITS + 8, 8); }
-    else if (rem == 17) { dls_lds_pass<THREADS, 9>(L, n, m, IDX_BITS, 9); dls_lds_pass<THREADS, 8>(L, n, m, IDX_BITS + 9, 8); }
-    else {
-        for (int pass = 0, lo = 0; pass < npass; pass++) {
-            const int nbits = dls_pass_bits(rem, lo, npass, pass);
-            dls_lds_pass<THREADS, 0>(L, n, m, IDX_BITS + lo, nbits);
-            lo += nbits;
-        }
-    }
-    // payload: position p takes the (id, rect) that arrived at index idx(p).  In place: every load lands before any store goes out
-    uint32_t v[DLS_ITEMS], r[DLS_ITEMS];
-#pragma unroll
-    for (int j = 0; j < DLS_ITEMS; j++) {
-        const uint32_t p = tid + j * DLS_THREADS;
-        v[j] = 0u; r[j] = 0u;
-        if (p < n) { const uint32_t idx = L.buf[p] & (DLS_CAP - 1u); v[j] = vb[s + idx]; r[j] = rb[s + idx]; }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < DLS_ITEMS; j++) {
-        const uint32_t p = tid + j * DLS_THREADS;
-        if (p < n) { vb[s + p] = v[j]; rb[s + p] = r[j]; if (local_incl) L.buf[p] = rect4_count(r[j]); }
-    }
+    dls_load_packed(L, kb + s, n, dq.kmin, rem);
+    dls_sort_words<THREADS, true>(L, n, IDX_BITS, rem);
+    dls_permute_payload(L, vb, rb, s, n, [&](uint32_t p) { return L.buf[p] & (DLS_CAP - 1u); }, local_incl != nullptr);
     if (local_incl) {
         __syncthreads();
         const uint32_t sum = dls_scan_chunk(L, n, 0u);
@@ -997,10 +1053,10 @@ __global__ __launch_bounds__(256) void duplicate_kernel(int P, int gx, int gy, c
     for (uint32_t tb = start; tb < end; tb += 64) {       // wave-uniform trip count
         const uint32_t t = tb + lane;
         s_mark[wave][lane] = 0u;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
         // Gaussians with instances whose first slot lies in this round (distinct slots: their ranges are disjoint)
         if (count != 0u && off - tb < 64u) s_mark[wave][off - tb] = (uint32_t)lane + 1u;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
         uint32_t owner = wave_inclusive_max_u32(s_mark[wave][lane]);
         owner = owner > carry ? owner : carry;
         carry = (uint32_t)__builtin_amdgcn_readlane((int)owner, 63);
@@ -1056,7 +1112,7 @@ __global__ __launch_bounds__(256) void tile_ranges_kernel(uint32_t R, const uint
 //              always is one.  Distinct values + repeated values <= list length = BINS.  ub holds the upper bounds in the doubled space
 //              K = 2 key + 1 (2 v closes "below v", 2 v + 1 closes "up to v"; keys are < 2^28 where the sort applies), padded with ~0:
 //              bucket(key) = number of entries below 2 key + 1.
-//   partition  histogram -> row scan -> scatter as in the MSD sort (stable: dls_rank, ballots or LDS atomics), the digit by a binary
+//   partition  histogram -> row scan -> scatter as in the MSD sort (stable: wave_rank, ballots or LDS atomics), the digit by a binary
 //              search of the table in LDS.
 //   buckets    a workgroup per bucket.  Its keys lie in [klo, khi] = what (ub[b - 1], ub[b]] admits.  klo == khi: every key is equal, the
 //              stable partition ordered it (every equality bucket, the invisible one among them: no special case).  Else the bucket is
@@ -1065,16 +1121,6 @@ __global__ __launch_bounds__(256) void tile_ranges_kernel(uint32_t R, const uint
 //              the passes the span's own width needs; a bucket beyond `cap` through memory (the sample is not a proof).
 #define SS_SAMPLE 8192
 __device__ unsigned long long g_ss_stats[8];      // developer census (option "depth_sort_sample_stats"): ex4d_debug_sample_sort
-
-template <int BINS>
-__device__ __forceinline__ uint32_t ss_bucket_of(const uint32_t *ub, uint32_t key)
-{
-    const uint32_t K = 2u * key + 1u;
-    uint32_t i = 0;
-#pragma unroll
-    for (uint32_t step = BINS / 2; step > 0; step >>= 1) if (ub[i + step - 1u] < K) i += step;      // (the last real entry is 2 inv + 1 >= K: i <= BINS - 1)
-    return i;
-}
 
 template <int BINS>
 __global__ __launch_bounds__(512) void ss_splitter_kernel(const uint32_t *__restrict__ keys, uint32_t n, uint32_t inv_key, int key_bits,
@@ -1093,13 +1139,7 @@ __global__ __launch_bounds__(512) void ss_splitter_kernel(const uint32_t *__rest
         for (int j = 0; j < DLS_ITEMS; j++) { const uint32_t p = tid + j * 512; if (p < ns) L.buf[p] = k[j]; }
     }
     __syncthreads();
-    const int npass = (key_bits + 8) / 9;
-    const uint32_t m = ((ns + 8 * 64 - 1) / (8 * 64)) * 64;
-    for (int pass = 0, lo = 0; pass < npass; pass++) {
-        const int nbits = dls_pass_bits(key_bits, lo, npass, pass);
-        dls_lds_pass<512, 0>(L, ns, m, lo, nbits);
-        lo += nbits;
-    }
+    dls_sort_words<512, false>(L, ns, 0, key_bits);
     constexpr uint32_t NSPL = BINS - 2;
     for (uint32_t j = tid; j < (uint32_t)BINS; j += 512) spl[j] = j < NSPL ? L.buf[((j + 1u) * ns) / (NSPL + 1u)] : inv_key;
     __syncthreads();
@@ -1133,169 +1173,8 @@ __global__ __launch_bounds__(512) void ss_splitter_kernel(const uint32_t *__rest
     if (stats && tid == 0) atomicAdd(&stats[7], (unsigned long long)(total >> 16));
 }
 
-template <int ITEMS, int BINS>
-__global__ __launch_bounds__(RS_THREADS) void ss_histogram_kernel(const uint32_t *__restrict__ keys, uint32_t n, uint32_t nblocks,
-    uint32_t *__restrict__ hist, const uint32_t *__restrict__ table)
-{
-    __shared__ uint32_t h[BINS];
-    __shared__ uint32_t ub[BINS];
-    for (int b = threadIdx.x; b < BINS; b += RS_THREADS) { h[b] = 0; ub[b] = table[b]; }
-    const uint32_t base = blockIdx.x * (RS_THREADS * ITEMS);
-    uint32_t k[ITEMS];
-    if (base < n) {
-#pragma unroll
-        for (int it = 0; it < ITEMS; it++) {
-            const uint32_t i = base + it * RS_THREADS + threadIdx.x;
-            k[it] = keys[i < n ? i : n - 1];
-        }
-    }
-    __syncthreads();
-    if (base < n) {
-#pragma unroll
-        for (int it = 0; it < ITEMS; it++) {
-            const uint32_t i = base + it * RS_THREADS + threadIdx.x;
-            if (i < n) atomicAdd(&h[ss_bucket_of<BINS>(ub, k[it])], 1u);
-        }
-    }
-    __syncthreads();
-    for (int b = threadIdx.x; b < BINS; b += RS_THREADS) hist[(size_t)b * nblocks + blockIdx.x] = h[b];
-}
-
-// the stable partition of the (key, id, packed rect) triples by bucket: rs_scatter_kernel's MODE 3 with the table's digit (the ids are
-// the item indices; workgroup 0 leaves the first output position of every bucket in bucket_starts)
-template <int ITEMS, int BINS>
-__global__ __launch_bounds__(RS_THREADS) void ss_scatter_kernel(const uint32_t *__restrict__ keys_in, const uint32_t *__restrict__ rects_in,
-    uint32_t *__restrict__ keys_out, uint32_t *__restrict__ vals_out, uint32_t *__restrict__ rects_out, uint32_t n, uint32_t nblocks,
-    const uint32_t *__restrict__ hist, const uint32_t *__restrict__ table, uint32_t *__restrict__ bucket_starts)
-{
-    constexpr uint32_t CHUNK = RS_THREADS * ITEMS;
-    constexpr int NBITS = BINS == 512 ? 9 : 10, BPT = BINS / RS_THREADS;
-    static_assert(BINS == 512 || BINS == 1024, "bucket counts of the sample sort");
-    if (blockIdx.x * CHUNK >= n) return;
-    __shared__ uint32_t wave_cnt[4][BINS];
-    __shared__ uint32_t local_start[BINS];
-    __shared__ uint32_t global_base[BINS];
-    __shared__ uint32_t ub[BINS];
-    __shared__ uint32_t scan_tmp[4];
-    __shared__ uint2 stage[CHUNK];
-    __shared__ uint32_t stage_r[CHUNK];
-    static_assert(sizeof(uint32_t) * (7 * BINS + 4) + sizeof(uint32_t) * 3 * CHUNK <= 80 * 1024, "ss_scatter_kernel: static LDS beyond 80 KB");
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int i = tid; i < BINS; i += RS_THREADS) { ub[i] = table[i]; wave_cnt[0][i] = 0; wave_cnt[1][i] = 0; wave_cnt[2][i] = 0; wave_cnt[3][i] = 0; }
-    const uint32_t block_first = blockIdx.x * CHUNK, block_end = n;
-    const uint32_t base = block_first + wave * (CHUNK / 4);
-    uint32_t pre_gt[BPT], pre_hb[BPT];
-#pragma unroll
-    for (int k = 0; k < BPT; k++) {
-        const int d = tid * BPT + k;
-        pre_gt[k] = hist[(size_t)BINS * nblocks + d];
-        pre_hb[k] = hist[(size_t)d * nblocks + blockIdx.x];
-    }
-    uint32_t key[ITEMS], pos[ITEMS], rct[ITEMS], dig[ITEMS];
-#pragma unroll
-    for (int it = 0; it < ITEMS; it++) {
-        const uint32_t i = base + it * 64 + lane;
-        const uint32_t ic = i < block_end ? i : block_end - 1;
-        key[it] = keys_in[ic];
-        rct[it] = rects_in[ic];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int it = 0; it < ITEMS; it++) {
-        const uint32_t i = base + it * 64 + lane;
-        dig[it] = ss_bucket_of<BINS>(ub, key[it]);
-        pos[it] = dls_rank<NBITS>(wave_cnt[wave], dig[it], NBITS, i < block_end, lane);
-    }
-    __syncthreads();
-    {
-        uint32_t c[BPT][4], tot[BPT];
-        uint32_t tsum = 0, gsum = 0;
-#pragma unroll
-        for (int k = 0; k < BPT; k++) {
-            const int d = tid * BPT + k;
-#pragma unroll
-            for (int w = 0; w < 4; w++) c[k][w] = wave_cnt[w][d];
-            tot[k] = c[k][0] + c[k][1] + c[k][2] + c[k][3];
-            tsum += tot[k]; gsum += pre_gt[k];
-        }
-        uint32_t x = tsum, gx = gsum;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t y = __shfl_up(x, o, 64), gy = __shfl_up(gx, o, 64);
-            if (lane >= o) { x += y; gx += gy; }
-        }
-        if (lane == 63) { scan_tmp[wave] = x; local_start[wave] = gx; }          // (local_start: free until the loop below)
-        __syncthreads();
-        uint32_t ls = x - tsum, gb = gx - gsum;
-        for (int w = 0; w < wave; w++) { ls += scan_tmp[w]; gb += local_start[w]; }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < BPT; k++) {
-            const int d = tid * BPT + k;
-            local_start[d] = ls;
-            global_base[d] = gb + pre_hb[k];
-            if (blockIdx.x == 0) bucket_starts[d] = gb;
-            wave_cnt[0][d] = ls; wave_cnt[1][d] = ls + c[k][0]; wave_cnt[2][d] = ls + c[k][0] + c[k][1]; wave_cnt[3][d] = ls + c[k][0] + c[k][1] + c[k][2];
-            ls += tot[k]; gb += pre_gt[k];
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int it = 0; it < ITEMS; it++) {
-        const uint32_t i = base + it * 64 + lane;
-        if (i < block_end) {
-            const uint32_t slot = wave_cnt[wave][dig[it]] + pos[it];
-            stage[slot] = make_uint2(key[it], i);
-            stage_r[slot] = rct[it];
-        }
-    }
-    __syncthreads();
-    const uint32_t count = (block_end - block_first) < CHUNK ? (block_end - block_first) : CHUNK;
-#pragma unroll 4
-    for (uint32_t p = tid; p < count; p += RS_THREADS) {
-        const uint2 kv = stage[p];
-        const uint32_t d = ss_bucket_of<BINS>(ub, kv.x);
-        const uint32_t dst = global_base[d] + (p - local_start[d]);
-        keys_out[dst] = kv.x; vals_out[dst] = kv.y; rects_out[dst] = stage_r[p];
-    }
-}
-
 // (the arrival index of the pair path in 16 bits: 64 KB with 512 threads, two workgroups per CU -- every bucket of 1.0 M Gaussians resident at once)
 template <int THREADS> struct SsLds { DlsLds<THREADS> L; uint16_t idx[THREADS * DLS_ITEMS]; };
-
-// one stable LSD pass over the n (key, arrival index) pairs in (L.buf, idx) on the digit (key >> lo) & (2^nbits - 1)
-template <int THREADS>
-__device__ __forceinline__ void ss_pair_pass(SsLds<THREADS> &S, uint32_t n, uint32_t m, int lo, int nbits)
-{
-    DlsLds<THREADS> &L = S.L;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t mask = (1u << nbits) - 1u;
-    const uint32_t wbase = wave * m;
-    for (int i = lane; i < (1 << nbits); i += 64) L.cnt[wave][i] = 0;
-    dls_wave_sync();
-    uint32_t word[DLS_ITEMS], idx[DLS_ITEMS], pos[DLS_ITEMS];
-#pragma unroll
-    for (int it = 0; it < DLS_ITEMS; it++) {
-        word[it] = 0u; idx[it] = 0u; pos[it] = 0u;
-        if ((uint32_t)(it * 64) < m) {                    // (wave-uniform)
-            const uint32_t i = wbase + it * 64 + lane;
-            const bool valid = i < n;
-            word[it] = valid ? L.buf[i] : 0u;
-            idx[it] = valid ? S.idx[i] : 0u;
-            pos[it] = dls_rank<0>(L.cnt[wave], (word[it] >> lo) & mask, nbits, valid, lane);
-        }
-    }
-    __syncthreads();
-    dls_scan_counts(L, nbits);
-#pragma unroll
-    for (int it = 0; it < DLS_ITEMS; it++) {
-        if ((uint32_t)(it * 64) < m) {
-            const uint32_t i = wbase + it * 64 + lane;
-            if (i < n) { const uint32_t dst = L.cnt[wave][(word[it] >> lo) & mask] + pos[it]; L.buf[dst] = word[it]; S.idx[dst] = (uint16_t)idx[it]; }
-        }
-    }
-    __syncthreads();
-}
 
 // census cells (stats): [0] empty buckets, [1] buckets skipped (one key value, or one Gaussian), [2] sorted on packed words, [3] on pairs,
 // [4] through memory, [5] Gaussians in those, [6] largest bucket that admits more than one key value, [7] distinct splitters (splitter kernel)
@@ -1304,12 +1183,12 @@ __global__ __launch_bounds__(THREADS) void ss_bucket_kernel(uint32_t *kb, uint32
     const uint32_t *__restrict__ starts, const uint32_t *__restrict__ totals, const uint32_t *__restrict__ table, uint32_t cap,
     int T, uint2 *__restrict__ ranges, unsigned long long *__restrict__ stats)
 {
-    constexpr int DLS_THREADS = THREADS, DLS_WAVES = THREADS / 64, DLS_CAP = THREADS * DLS_ITEMS, IDX_BITS = DlsLds<THREADS>::IDX_BITS;
+    constexpr int DLS_CAP = THREADS * DLS_ITEMS, IDX_BITS = DlsLds<THREADS>::IDX_BITS;
     __shared__ SsLds<THREADS> S;
     DlsLds<THREADS> &L = S.L;
     const uint32_t b = blockIdx.x;
     const int tid = threadIdx.x;
-    if (ranges) for (int i = b * DLS_THREADS + tid; i < T; i += gridDim.x * DLS_THREADS) ranges[i] = make_uint2(0u, 0u);
+    zero_tile_ranges<THREADS>(ranges, (uint32_t)T);
     const uint32_t n = totals[b], s = starts[b];
     if (n == 0u) { if (stats && tid == 0) atomicAdd(&stats[0], 1ull); return; }
     const uint32_t ub_prev = b ? table[b - 1u] : 0u, ub_cur = table[b];
@@ -1325,40 +1204,26 @@ __global__ __launch_bounds__(THREADS) void ss_bucket_kernel(uint32_t *kb, uint32
     }
     const bool packed = rem + IDX_BITS <= 32;
     if (stats && tid == 0) atomicAdd(&stats[packed ? 2 : 3], 1ull);
-    {
+    if (packed) {
+        dls_load_packed(L, kb + s, n, klo, rem);
+        dls_sort_words<THREADS, false>(L, n, IDX_BITS, rem);
+    } else {
+        // a span too wide for the word: (key - klo, arrival index) pairs in two LDS arrays
         uint32_t k[DLS_ITEMS];                           // every load in flight before the first LDS store
 #pragma unroll
-        for (int j = 0; j < DLS_ITEMS; j++) { const uint32_t p = tid + j * DLS_THREADS; k[j] = p < n ? kb[s + p] : 0u; }
+        for (int j = 0; j < DLS_ITEMS; j++) { const uint32_t p = tid + j * THREADS; k[j] = p < n ? kb[s + p] : 0u; }
 #pragma unroll
-        for (int j = 0; j < DLS_ITEMS; j++) {
-            const uint32_t p = tid + j * DLS_THREADS;
-            if (p < n) { if (packed) L.buf[p] = ((k[j] - klo) << IDX_BITS) | p; else { L.buf[p] = k[j] - klo; S.idx[p] = (uint16_t)p; } }
+        for (int j = 0; j < DLS_ITEMS; j++) { const uint32_t p = tid + j * THREADS; if (p < n) { L.buf[p] = k[j] - klo; S.idx[p] = (uint16_t)p; } }
+        __syncthreads();
+        const int npass = dls_passes(rem);
+        const uint32_t m = ((n + THREADS - 1) / THREADS) * 64;          // items per wave: a multiple of 64, <= 1024
+        for (int pass = 0, lo = 0; pass < npass; pass++) {
+            const int nbits = dls_pass_bits(rem, lo, npass, pass);
+            dls_lds_pass<THREADS, 0>(L, n, m, lo, nbits, S.idx);
+            lo += nbits;
         }
     }
-    __syncthreads();
-    const int npass = (rem + 8) / 9;
-    const uint32_t m = ((n + DLS_WAVES * 64 - 1) / (DLS_WAVES * 64)) * 64;          // items per wave: a multiple of 64, <= 1024
-    for (int pass = 0, lo = 0; pass < npass; pass++) {
-        const int nbits = dls_pass_bits(rem, lo, npass, pass);
-        if (packed) dls_lds_pass<THREADS, 0>(L, n, m, IDX_BITS + lo, nbits);
-        else ss_pair_pass<THREADS>(S, n, m, lo, nbits);
-        lo += nbits;
-    }
-    // payload: position p takes the (id, rect) that arrived at index idx(p).  In place: every load lands before any store goes out
-    uint32_t v[DLS_ITEMS], r[DLS_ITEMS];
-#pragma unroll
-    for (int j = 0; j < DLS_ITEMS; j++) {
-        const uint32_t p = tid + j * DLS_THREADS;
-        v[j] = 0u; r[j] = 0u;
-        if (p < n) { const uint32_t idx = packed ? (L.buf[p] & (DLS_CAP - 1u)) : S.idx[p]; v[j] = vb[s + idx]; r[j] = rb[s + idx]; }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < DLS_ITEMS; j++) {
-        const uint32_t p = tid + j * DLS_THREADS;
-        if (p < n) { vb[s + p] = v[j]; rb[s + p] = r[j]; }
-    }
+    dls_permute_payload(L, vb, rb, s, n, [&](uint32_t p) { return packed ? (L.buf[p] & (DLS_CAP - 1u)) : (uint32_t)S.idx[p]; }, false);
 }
 
 }  // namespace
@@ -1425,22 +1290,20 @@ hipError_t ex4d_radix_sort_pairs(uint32_t *keys_a, uint32_t *vals_a, uint32_t *k
     const int npass = ex4d_radix_passes(n, end_bit);
     for (int pass = 0, shift = 0; pass < npass; pass++) {
         const int nbits = (end_bit - shift + (npass - pass) - 1) / (npass - pass);
-        const uint32_t mask = (1u << nbits) - 1u;
+        const DigitBitsArgs da = { shift, nbits };
+        const bool last = pass == npass - 1;
+#define RS_PASS_SCATTER(ITEMS, BINS, NB) hipLaunchKernelGGL((rs_scatter_kernel<ITEMS, BINS, 0, DigitBits<NB>>), dim3(nb), dim3(RS_THREADS), 0, stream, kin, vin, kout, vout, n, da, nb, hist, 0, nullptr, 0, \
+            last ? zero_ranges : (uint2 *)nullptr, n_dev, last ? gather_in : (const uint32_t *)nullptr, last ? gather_out : (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t)num_ranges)
         if (small) {
-            hipLaunchKernelGGL((rs_histogram_kernel<RS_SMALL_ITEMS, 512, 1>), dim3(nb), dim3(RS_THREADS), 0, stream, kin, n, shift, mask, nb, hist, n_dev);
+            hipLaunchKernelGGL((rs_histogram_kernel<RS_SMALL_ITEMS, 512, 1, DigitBits<0>>), dim3(nb), dim3(RS_THREADS), 0, stream, kin, n, nb, hist, n_dev, da);
             hipLaunchKernelGGL(rs_scan_rows_kernel, dim3(1u << nbits), dim3(256), 0, stream, nb, hist, 512u);
-            const bool last = pass == npass - 1;
-#define RS_SMALL_SCATTER(NB) hipLaunchKernelGGL((rs_scatter_kernel<RS_SMALL_ITEMS, 512, 0, NB>), dim3(nb), dim3(RS_THREADS), 0, stream, kin, vin, kout, vout, n, shift, nbits, nb, hist, 0, nullptr, 0, \
-                last ? zero_ranges : (uint2 *)nullptr, n_dev, last ? gather_in : (const uint32_t *)nullptr, last ? gather_out : (uint32_t *)nullptr, (uint32_t *)nullptr, (const uint32_t *)nullptr, (uint32_t)num_ranges)
-            if (nbits == 9) RS_SMALL_SCATTER(9); else if (nbits == 8) RS_SMALL_SCATTER(8); else RS_SMALL_SCATTER(0);
-#undef RS_SMALL_SCATTER
+            if (nbits == 9) RS_PASS_SCATTER(RS_SMALL_ITEMS, 512, 9); else if (nbits == 8) RS_PASS_SCATTER(RS_SMALL_ITEMS, 512, 8); else RS_PASS_SCATTER(RS_SMALL_ITEMS, 512, 0);
         } else {
-            hipLaunchKernelGGL((rs_histogram_kernel<RS_ITEMS, 256, 1>), dim3(nb), dim3(RS_THREADS), 0, stream, kin, n, shift, mask, nb, hist, n_dev);
+            hipLaunchKernelGGL((rs_histogram_kernel<RS_ITEMS, 256, 1, DigitBits<0>>), dim3(nb), dim3(RS_THREADS), 0, stream, kin, n, nb, hist, n_dev, da);
             hipLaunchKernelGGL(rs_scan_rows_kernel, dim3(1u << nbits), dim3(256), 0, stream, nb, hist, 256u);
-            const bool last = pass == npass - 1;
-            hipLaunchKernelGGL((rs_scatter_kernel<RS_ITEMS, 256, 0, 0>), dim3(nb), dim3(RS_THREADS), 0, stream, kin, vin, kout, vout, n, shift, nbits, nb, hist, 0, nullptr, 0,
-                last ? zero_ranges : (uint2 *)nullptr, n_dev, last ? gather_in : (const uint32_t *)nullptr, last ? gather_out : (uint32_t *)nullptr, (uint32_t *)nullptr, (const uint32_t *)nullptr, (uint32_t)num_ranges);
+            RS_PASS_SCATTER(RS_ITEMS, 256, 0);
         }
+#undef RS_PASS_SCATTER
         uint32_t *t = kin; kin = kout; kout = t;
         t = (pass == 0) ? vnext : vin; vin = vout; vout = t;
         *result_in_a = !*result_in_a;
@@ -1466,6 +1329,30 @@ int ex4d_depth_sort_msd_bits(uint32_t n, int key_bits)
     const int narrow = EX4D_DLS_MSD_BITS - 1;
     return (n <= 1300000u && key_bits - (narrow - 1) + DLS_IDX_BITS <= 32) ? narrow : EX4D_DLS_MSD_BITS;
 }
+// What the MSD and the sample depth sort launch alike: the partition of the (key, id, rect) triples by DIGIT -- histogram, row scan,
+// scatter; 8 or 16 items per thread by n -- and the kernel that finishes the buckets: 256 or 512 threads (local_threads, or default_threads
+// where that names neither), `local_cap` clamped to what they hold in LDS.  bucket(threads, bucket totals, capacity) launches that kernel.
+template <class DIGIT, int BINS, class BUCKET>
+static hipError_t depth_sort_launch(const uint32_t *ka, const uint32_t *ra, uint32_t *kb, uint32_t *vb, uint32_t *rb, uint32_t n, uint32_t *hist, uint32_t *starts,
+    typename DIGIT::Args da, int local_threads, int default_threads, uint32_t local_cap, hipStream_t stream, BUCKET bucket)
+{
+    const uint32_t nb = rs_blocks_for(n);
+    if (local_threads != 256 && local_threads != 512) local_threads = default_threads;
+    const uint32_t kcap = (uint32_t)local_threads * DLS_ITEMS;
+    if (local_cap == 0 || local_cap > kcap) local_cap = kcap;
+    auto partition = [&](auto items) {
+        constexpr int ITEMS = decltype(items)::value;
+        hipLaunchKernelGGL((rs_histogram_kernel<ITEMS, BINS, 1, DIGIT>), dim3(nb), dim3(RS_THREADS), 0, stream, ka, n, nb, hist, (const uint32_t *)nullptr, da);
+        hipLaunchKernelGGL(rs_scan_rows_kernel, dim3(BINS), dim3(256), 0, stream, nb, hist, (uint32_t)BINS);
+        hipLaunchKernelGGL((rs_scatter_kernel<ITEMS, BINS, 3, DIGIT>), dim3(nb), dim3(RS_THREADS), 0, stream, ka, (const uint32_t *)nullptr, kb, vb, n, da, nb, (const uint32_t *)hist,
+            0, (const uint32_t *)nullptr, 0, (uint2 *)nullptr, (const uint32_t *)nullptr, ra, rb, starts);
+    };
+    if (rs_items_for(n) == RS_SMALL_ITEMS) partition(std::integral_constant<int, RS_SMALL_ITEMS>{}); else partition(std::integral_constant<int, RS_ITEMS>{});
+    const uint32_t *totals = hist + (size_t)BINS * nb;
+    if (local_threads == 256) bucket(std::integral_constant<int, 256>{}, totals, local_cap); else bucket(std::integral_constant<int, 512>{}, totals, local_cap);
+    return hipGetLastError();
+}
+
 template <int MB>
 static hipError_t depth_sort_msd_launch(uint32_t *ka, uint32_t *va, uint32_t *ra, uint32_t *kb, uint32_t *vb, uint32_t *rb, uint32_t n, uint32_t inv_key,
     uint32_t *flags, const uint2 *wave_ranges, uint32_t *hist, uint32_t *starts, uint32_t local_cap, hipStream_t stream,
@@ -1473,31 +1360,16 @@ static hipError_t depth_sort_msd_launch(uint32_t *ka, uint32_t *va, uint32_t *ra
 {
     if (n == 0) return hipSuccess;
     constexpr int BINS = 1 << MB;
-    const uint32_t nb = rs_blocks_for(n);
-    const bool small = rs_items_for(n) == RS_SMALL_ITEMS;
     uint32_t *dparams = flags + EX4D_FLAG_DPARAMS;
     const uint32_t nranges = (n + 255u) / 256u;          // one (max key, max ~key) pair per workgroup of the per-Gaussian kernel
-    if (local_threads != 256 && local_threads != 512) local_threads = (MB < EX4D_DLS_MSD_BITS || n > 1200000u) ? 512 : 256;      // (the 9-bit digit's buckets are twice as large)
-    const uint32_t kcap = (uint32_t)local_threads * DLS_ITEMS;
-    if (local_cap == 0 || local_cap > kcap) local_cap = kcap;
-    if (small) {
-        hipLaunchKernelGGL((dls_histogram_kernel<RS_SMALL_ITEMS, BINS>), dim3(nb), dim3(RS_THREADS), 0, stream, ka, n, nb, hist, dparams, wave_ranges, nranges, inv_key);
-        hipLaunchKernelGGL(rs_scan_rows_kernel, dim3(BINS), dim3(256), 0, stream, nb, hist, (uint32_t)BINS);
-        hipLaunchKernelGGL((rs_scatter_kernel<RS_SMALL_ITEMS, BINS, 3, MB>), dim3(nb), dim3(RS_THREADS), 0, stream, ka, (const uint32_t *)nullptr, kb, vb, n, 0, MB, nb, hist,
-            0, (const uint32_t *)nullptr, 0, (uint2 *)nullptr, (const uint32_t *)nullptr, ra, rb, starts, (const uint32_t *)dparams);
-    } else {
-        hipLaunchKernelGGL((dls_histogram_kernel<RS_ITEMS, BINS>), dim3(nb), dim3(RS_THREADS), 0, stream, ka, n, nb, hist, dparams, wave_ranges, nranges, inv_key);
-        hipLaunchKernelGGL(rs_scan_rows_kernel, dim3(BINS), dim3(256), 0, stream, nb, hist, (uint32_t)BINS);
-        hipLaunchKernelGGL((rs_scatter_kernel<RS_ITEMS, BINS, 3, MB>), dim3(nb), dim3(RS_THREADS), 0, stream, ka, (const uint32_t *)nullptr, kb, vb, n, 0, MB, nb, hist,
-            0, (const uint32_t *)nullptr, 0, (uint2 *)nullptr, (const uint32_t *)nullptr, ra, rb, starts, (const uint32_t *)dparams);
-    }
-    if (local_threads == 256)
-        hipLaunchKernelGGL(depth_local_sort_kernel<256>, dim3(BINS), dim3(256), 0, stream, kb, vb, rb, ka, va, ra, starts, hist + (size_t)BINS * nb, (const uint32_t *)dparams, local_cap,
-            local_incl, bucket_sums, T, ranges, watch);
-    else
-        hipLaunchKernelGGL(depth_local_sort_kernel<512>, dim3(BINS), dim3(512), 0, stream, kb, vb, rb, ka, va, ra, starts, hist + (size_t)BINS * nb, (const uint32_t *)dparams, local_cap,
-            local_incl, bucket_sums, T, ranges, watch);
-    return hipGetLastError();
+    const typename DigitRange<BINS>::Args da = { dparams, wave_ranges, nranges, inv_key };
+    const int default_threads = (MB < EX4D_DLS_MSD_BITS || n > 1200000u) ? 512 : 256;      // (the 9-bit digit's buckets are twice as large)
+    return depth_sort_launch<DigitRange<BINS>, BINS>(ka, ra, kb, vb, rb, n, hist, starts, da, local_threads, default_threads, local_cap, stream,
+        [&](auto threads, const uint32_t *totals, uint32_t cap) {
+            constexpr int THREADS = decltype(threads)::value;
+            hipLaunchKernelGGL(depth_local_sort_kernel<THREADS>, dim3(BINS), dim3(THREADS), 0, stream, kb, vb, rb, ka, va, ra, (const uint32_t *)starts, totals, (const uint32_t *)dparams, cap,
+                local_incl, bucket_sums, T, ranges, watch);
+        });
 }
 
 hipError_t ex4d_depth_sort_msd(uint32_t *ka, uint32_t *va, uint32_t *ra, uint32_t *kb, uint32_t *vb, uint32_t *rb, uint32_t n, uint32_t inv_key,
@@ -1516,29 +1388,13 @@ template <int BINS>
 static hipError_t depth_sort_sample_launch(uint32_t *ka, uint32_t *va, uint32_t *ra, uint32_t *kb, uint32_t *vb, uint32_t *rb, uint32_t n, uint32_t inv_key, int key_bits,
     uint32_t *hist, uint32_t *starts, uint32_t *table, uint32_t local_cap, hipStream_t stream, int T, uint2 *ranges, int local_threads, unsigned long long *stats)
 {
-    const uint32_t nb = rs_blocks_for(n);
-    if (local_threads != 256 && local_threads != 512) local_threads = 512;
-    const uint32_t kcap = (uint32_t)local_threads * DLS_ITEMS;
-    if (local_cap == 0 || local_cap > kcap) local_cap = kcap;
     hipLaunchKernelGGL(ss_splitter_kernel<BINS>, dim3(1), dim3(512), 0, stream, (const uint32_t *)ka, n, inv_key, key_bits, table, stats);
-    if (rs_items_for(n) == RS_SMALL_ITEMS) {
-        hipLaunchKernelGGL((ss_histogram_kernel<RS_SMALL_ITEMS, BINS>), dim3(nb), dim3(RS_THREADS), 0, stream, (const uint32_t *)ka, n, nb, hist, (const uint32_t *)table);
-        hipLaunchKernelGGL(rs_scan_rows_kernel, dim3(BINS), dim3(256), 0, stream, nb, hist, (uint32_t)BINS);
-        hipLaunchKernelGGL((ss_scatter_kernel<RS_SMALL_ITEMS, BINS>), dim3(nb), dim3(RS_THREADS), 0, stream, (const uint32_t *)ka, (const uint32_t *)ra, kb, vb, rb, n, nb,
-            (const uint32_t *)hist, (const uint32_t *)table, starts);
-    } else {
-        hipLaunchKernelGGL((ss_histogram_kernel<RS_ITEMS, BINS>), dim3(nb), dim3(RS_THREADS), 0, stream, (const uint32_t *)ka, n, nb, hist, (const uint32_t *)table);
-        hipLaunchKernelGGL(rs_scan_rows_kernel, dim3(BINS), dim3(256), 0, stream, nb, hist, (uint32_t)BINS);
-        hipLaunchKernelGGL((ss_scatter_kernel<RS_ITEMS, BINS>), dim3(nb), dim3(RS_THREADS), 0, stream, (const uint32_t *)ka, (const uint32_t *)ra, kb, vb, rb, n, nb,
-            (const uint32_t *)hist, (const uint32_t *)table, starts);
-    }
-    if (local_threads == 256)
-        hipLaunchKernelGGL(ss_bucket_kernel<256>, dim3(BINS), dim3(256), 0, stream, kb, vb, rb, ka, va, ra, (const uint32_t *)starts, (const uint32_t *)(hist + (size_t)BINS * nb),
-            (const uint32_t *)table, local_cap, T, ranges, stats);
-    else
-        hipLaunchKernelGGL(ss_bucket_kernel<512>, dim3(BINS), dim3(512), 0, stream, kb, vb, rb, ka, va, ra, (const uint32_t *)starts, (const uint32_t *)(hist + (size_t)BINS * nb),
-            (const uint32_t *)table, local_cap, T, ranges, stats);
-    return hipGetLastError();
+    const typename DigitTable<BINS>::Args da = { table };
+    return depth_sort_launch<DigitTable<BINS>, BINS>(ka, ra, kb, vb, rb, n, hist, starts, da, local_threads, 512, local_cap, stream,
+        [&](auto threads, const uint32_t *totals, uint32_t cap) {
+            constexpr int THREADS = decltype(threads)::value;
+            hipLaunchKernelGGL(ss_bucket_kernel<THREADS>, dim3(BINS), dim3(THREADS), 0, stream, kb, vb, rb, ka, va, ra, (const uint32_t *)starts, totals, (const uint32_t *)table, cap, T, ranges, stats);
+        });
 }
 
 int ex4d_depth_sort_sample_bins(uint32_t n) { return n <= 1300000u ? 512 : 1024; }
@@ -1559,7 +1415,7 @@ hipError_t ex4d_sample_sort_stats(unsigned long long *out8, int reset)
     return e;
 }
 
-// ---- MSD tile sort (see ts_block_table_kernel).  Applies when the tile id needs 9..16 bits and the Gaussian ids fit under the low digit.
+// ---- MSD tile sort (see ts_histogram_kernel above).  Applies when the tile id needs 9..16 bits and the Gaussian ids fit under the low digit.
 bool ex4d_tile_sort_msd_applies(int P, int tile_bits)
 {
     if (tile_bits < 9 || tile_bits > 16) return false;
@@ -1581,16 +1437,17 @@ hipError_t ex4d_tile_sort_msd(const uint32_t *keys, const uint32_t *vals, uint32
     const uint32_t nbA = rs_num_blocks(R), nbB = ts_max_blocks(R, tile_bits);
     uint32_t *histB = hist + (size_t)256 * (nbA + 1);
     const uint32_t *totals = hist + (size_t)256 * nbA;
-    hipLaunchKernelGGL((rs_histogram_kernel<RS_ITEMS, 256, 8>), dim3(nbA), dim3(RS_THREADS), 0, stream, keys, R, low_bits, (1u << high_bits) - 1u, nbA, hist, n_dev);
+    const DigitBitsArgs daA = { low_bits, high_bits }, daB = { 32 - low_bits, low_bits };
+    hipLaunchKernelGGL((rs_histogram_kernel<RS_ITEMS, 256, 8, DigitBits<0>>), dim3(nbA), dim3(RS_THREADS), 0, stream, keys, R, nbA, hist, n_dev, daA);
     hipLaunchKernelGGL(rs_scan_rows_kernel, dim3(1u << high_bits), dim3(256), 0, stream, nbA, hist, 256u);
-#define TS_SCATTER_A(NB) hipLaunchKernelGGL((rs_scatter_kernel<RS_ITEMS, 256, 1, NB>), dim3(nbA), dim3(RS_THREADS), 0, stream, keys, vals, packed, (uint32_t *)nullptr, \
-        R, low_bits, high_bits, nbA, hist, low_bits, (const uint32_t *)nullptr, 0, (uint2 *)nullptr, n_dev)
+#define TS_SCATTER_A(NB) hipLaunchKernelGGL((rs_scatter_kernel<RS_ITEMS, 256, 1, DigitBits<NB>>), dim3(nbA), dim3(RS_THREADS), 0, stream, keys, vals, packed, (uint32_t *)nullptr, \
+        R, daA, nbA, (const uint32_t *)hist, low_bits, (const uint32_t *)nullptr, 0, (uint2 *)nullptr, n_dev)
     if (high_bits == 6) TS_SCATTER_A(6); else if (high_bits == 7) TS_SCATTER_A(7); else if (high_bits == 8) TS_SCATTER_A(8); else TS_SCATTER_A(0);
 #undef TS_SCATTER_A
     hipLaunchKernelGGL(ts_histogram_kernel, dim3(nbB), dim3(RS_THREADS), 0, stream, packed, totals, 1 << high_bits, 32 - low_bits, nbB, histB);
     hipLaunchKernelGGL(rs_scan_rows_kernel, dim3(1u << low_bits), dim3(256), 0, stream, nbB, histB, 256u);
-#define TS_SCATTER_B(NB) hipLaunchKernelGGL((rs_scatter_kernel<RS_ITEMS, 256, 2, NB>), dim3(nbB), dim3(RS_THREADS), 0, stream, packed, (const uint32_t *)nullptr, tile_ids_out, point_list, \
-        R, 32 - low_bits, low_bits, nbB, histB, low_bits, totals, 1 << high_bits, ranges, (const uint32_t *)nullptr)
+#define TS_SCATTER_B(NB) hipLaunchKernelGGL((rs_scatter_kernel<RS_ITEMS, 256, 2, DigitBits<NB>>), dim3(nbB), dim3(RS_THREADS), 0, stream, packed, (const uint32_t *)nullptr, tile_ids_out, point_list, \
+        R, daB, nbB, (const uint32_t *)histB, low_bits, totals, 1 << high_bits, ranges, (const uint32_t *)nullptr)
     if (low_bits == 7) TS_SCATTER_B(7); else if (low_bits == 8) TS_SCATTER_B(8); else TS_SCATTER_B(0);
 #undef TS_SCATTER_B
     return hipGetLastError();
@@ -1607,11 +1464,12 @@ hipError_t ex4d_tile_sort_pass_b(const uint32_t *packed, const uint32_t *totals,
 {
     if (R == 0) return hipSuccess;
     const uint32_t nbB = ex4d_tile_sort_pass_b_blocks(R, nbuckets);
+    const DigitBitsArgs daB = { 32 - low_bits, low_bits };
     hipLaunchKernelGGL(ts_histogram_kernel, dim3(nbB), dim3(RS_THREADS), 0, stream, packed, totals, nbuckets, 32 - low_bits, nbB, histB, cap, block_table);
     hipLaunchKernelGGL(rs_scan_rows_kernel, dim3(1u << low_bits), dim3(256), 0, stream, nbB, histB, 256u);
-#define TS_SCATTER_B(NB) hipLaunchKernelGGL((rs_scatter_kernel<RS_ITEMS, 256, 2, NB>), dim3(nbB), dim3(RS_THREADS), 0, stream, packed, (const uint32_t *)nullptr, tile_ids_out, point_list, \
-        R, 32 - low_bits, low_bits, nbB, histB, low_bits, totals, nbuckets, ranges, (const uint32_t *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, \
-        (const uint32_t *)nullptr, stride, cap, block_table)
+#define TS_SCATTER_B(NB) hipLaunchKernelGGL((rs_scatter_kernel<RS_ITEMS, 256, 2, DigitBits<NB>>), dim3(nbB), dim3(RS_THREADS), 0, stream, packed, (const uint32_t *)nullptr, tile_ids_out, point_list, \
+        R, daB, nbB, (const uint32_t *)histB, low_bits, totals, nbuckets, ranges, (const uint32_t *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, \
+        stride, cap, block_table)
     if (low_bits == 7) TS_SCATTER_B(7); else if (low_bits == 8) TS_SCATTER_B(8); else TS_SCATTER_B(0);
 #undef TS_SCATTER_B
     return hipGetLastError();

@@ -4,7 +4,7 @@ census) and tests/test_gpu_binning_edges.py (every kernel chain against the rest
 
 The binning is ex4dgs_amd/csrc/ex4d_rowsort.hip (the row-segment sort: rows_seg_hist_kernel, rows_scan_kernel,
 rows_seg_scatter_kernel<NRP, CAP>) and ex4dgs_amd/csrc/ex4d_binning.hip (the pair sorts: rs_histogram_kernel / rs_scatter_kernel in
-its modes, ts_histogram_kernel, ts_locate_block; pass B; duplicate_kernel; scan_tiles_local_kernel).  The census restates, from the
+its modes with the DigitBits rule, ts_histogram_kernel, ts_locate_block; pass B; duplicate_kernel; scan_tiles_local_kernel).  The census restates, from the
 host code (ex4d_tile_sort_rows, ex4d_tile_sort_msd, ex4d_tile_sort_pass_b, ex4d_radix_sort_pairs, forward_impl) and from the kernels,
 WHICH template instantiation a frame launches and WHICH uniform branch every workgroup takes -- as names, so that a cell nobody
 reaches can be printed.

@@ -3,7 +3,8 @@ frame realises its plan on the CPU oracle; the frames reach every cell of the ce
 tests/test_gpu_depth_sort_edges.py (every kernel chain against the restatement, the census against the frame).
 
 The depth sort is either the LSD radix sort (ex4dgs_amd/csrc/ex4d_binning.hip: ex4d_radix_sort_pairs, driven from forward_impl in
-ex4d_api.hip) or the MSD-first sort (dls_histogram_kernel, rs_scatter_kernel mode 3, depth_local_sort_kernel<256 | 512>).  Which
+ex4d_api.hip) or the MSD-first sort (rs_histogram_kernel and rs_scatter_kernel mode 3 with the DigitRange rule,
+depth_local_sort_kernel<256 | 512>).  Which
 of their paths a frame takes depends on the two depth planes (the key is bits(p_view.z) - bits(min_depth); its width follows from the
 planes alone) and on the keys the frame occupies (the MSD sort cuts its top digit from [kmin, kmax]; what is left, `rem` bits, is
 sorted inside a bucket).  A frame here is a pair of planes and a list of keys in designed order: key k in [1, invisible - 1] is the

@@ -235,6 +235,37 @@ def test_the_census_constants_are_the_sources():
     assert _one(r"if \(rem == (\d+)\) \{ dls_lds_pass<THREADS, 8>", b) == "16" and _one(r"else if \(rem == (\d+)\) \{ dls_lds_pass<THREADS, 9>", b) == "17"
 
 
+def test_profile_tool_names_the_stage_of_recorded_and_current_sort_kernels():
+    """tools/pmc_traffic.py maps a kernel name to a stage by the first matching substring: the names the profiles up to round 6 recorded
+    and the names of the folded kernels (digit rule as the last template argument) land in the same stages."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("pmc_traffic", os.path.join(os.path.dirname(CSRC), "..", "tools", "pmc_traffic.py"))
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+    ns = "void (anonymous namespace)::"
+    for name, stage in (("dls_histogram_kernel<8, 512>(unsigned int const*", "depth_sort_msd_histogram"),
+                        ("rs_histogram_kernel<8, 512, 1, (anonymous namespace)::DigitRange<512> >(", "depth_sort_msd_histogram"),
+                        ("rs_histogram_kernel<16, 1024, 1, (anonymous namespace)::DigitTable<1024> >(", "depth_sort_sample_histogram"),
+                        ("rs_histogram_kernel<8, 512, 1>(", "depth_sort_histogram_pass"),
+                        ("rs_histogram_kernel<8, 512, 1, (anonymous namespace)::DigitBits<0> >(", "depth_sort_histogram_pass"),
+                        ("rs_histogram_kernel<16, 256, 8>(", "tile_sort_histogram_pass"),
+                        ("rs_histogram_kernel<16, 256, 8, (anonymous namespace)::DigitBits<0> >(", "tile_sort_histogram_pass"),
+                        ("rs_scatter_kernel<8, 512, 3, 9>(", "depth_sort_scatter_pass"),
+                        ("rs_scatter_kernel<8, 512, 3, (anonymous namespace)::DigitRange<512> >(", "depth_sort_scatter_pass"),
+                        ("rs_scatter_kernel<8, 512, 3, (anonymous namespace)::DigitTable<512> >(", "depth_sort_scatter_pass"),
+                        ("rs_scatter_kernel<16, 1024, 3, 10>(", "depth_sort_scatter_pass"),
+                        ("rs_scatter_kernel<16, 1024, 3, (anonymous namespace)::DigitTable<1024> >(", "depth_sort_scatter_pass"),
+                        ("rs_scatter_kernel<16, 512, 3, (anonymous namespace)::DigitRange<512> >(", "depth_sort_scatter_pass"),
+                        ("rs_scatter_kernel<16, 256, 0, (anonymous namespace)::DigitBits<0> >(", "depth_sort_scatter_pass"),
+                        ("rs_scatter_kernel<16, 256, 1, (anonymous namespace)::DigitBits<6> >(", "tile_sort_scatter_pass"),
+                        ("rs_histogram_kernel<16, 256, 1, (anonymous namespace)::DigitBits<0> >(", "depth_sort_histogram_pass"),
+                        ("rs_scatter_kernel<16, 256, 2, 7>(", "tile_sort_scatter_pass"),
+                        ("rs_scatter_kernel<16, 256, 2, (anonymous namespace)::DigitBits<7> >(", "tile_sort_scatter_pass"),
+                        ("depth_local_sort_kernel<512>(", "depth_sort_bucket_pass"), ("ss_bucket_kernel<512>(", "depth_sort_bucket_pass"),
+                        ("ss_splitter_kernel<512>(", "depth_sort_sample_splitters"), ("ts_histogram_kernel(", "tile_sort_histogram_pass_b")):
+        assert tool.alias(ns + name) == stage, name
+
+
 # ------------------------------------------------------------------------------------------------ the factored scene builder
 def _scene_as_before(name):
     """binning_cases.scene as it was before build_scene was factored out of it, word for word"""

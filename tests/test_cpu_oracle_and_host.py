@@ -659,7 +659,7 @@ __global__ void k(float *out, const float *in, unsigned *mask)
 
 
 def test_msd_depth_sort_index_arithmetic_restated_with_numpy():
-    """The optional MSD depth sort (ex4d_binning.hip: dls_range_kernel / dls_digit / depth_local_sort_kernel, duplicate_kernel's bucket
+    """The optional MSD depth sort (ex4d_binning.hip: dls_reduce_ranges / dls_digit / depth_local_sort_kernel, duplicate_kernel's bucket
     form) restated with numpy, so that a mistake in its arithmetic shows up without a GPU: the top digit cut from the occupied key range
     (invisible key -> last digit), a stable partition by digit, every bucket ordered by sorting the words `low key bits << 12 | arrival
     index`, the tile scan as bucket-local inclusive scans + bucket sums -- against a stable argsort of the keys and a plain exclusive

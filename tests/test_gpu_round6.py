@@ -59,7 +59,9 @@ def test_clustered_scene_tile_sorts_agree(hip_lib):
 def test_msd_depth_sort_above_two_million_gaussians(hip_lib):
     """beyond 2 M Gaussians the MSD depth sort's partition runs with 16 items per thread (72 KB of LDS), its histogram kernel
     likewise, and the bucket kernel with 512 threads at real bucket sizes -- MSD = LSD = a stable host sort there too; the row-segment
-    tile sort behind both (forward only: the image and the lists)."""
+    tile sort behind both (forward only: the image and the lists).  The sample depth sort runs the same partition kernel with its table
+    digit (16 items per thread, 1024 buckets), and with ballot ranking the MSD sort runs it without the LDS atomics: the same lists."""
+    from ex4dgs_amd import _C
     from tests.test_gpu_round5 import _host_depth_order
     ins, st = h.scene_inputs("cfg2", P=2_100_000)
     ins = {k: v.cuda() for k, v in ins.items()}
@@ -68,6 +70,16 @@ def test_msd_depth_sort_above_two_million_gaussians(hip_lib):
     assert torch.equal(lsd["depth_order"], _host_depth_order(lsd)), "LSD depth order differs from the host sort"
     _same(msd, lsd, "msd vs lsd at 2.1 M")
     _same(_frame(ins, st, depth_sort_msd=2, tile_sort_rows=0), lsd, "msd + pair sort vs lsd at 2.1 M")
+    try:
+        _C.set_option("depth_sort_sample", 1)                # (clears "depth_sort_sample_frames")
+        sample = _frame(ins, st)
+        assert _C.get_option("depth_sort_sample_frames") == 1, "the frame did not take the sample sort"
+        _same(sample, lsd, "sample sort vs lsd at 2.1 M")
+        _C.set_option("depth_sort_sample", 0)
+        _same(_frame(ins, st, rank_lds_atomics=0, depth_sort_msd=2), lsd, "msd with ballot ranking vs lsd at 2.1 M")
+    finally:
+        _C.set_option("depth_sort_sample", 0)
+        _C.set_option("rank_lds_atomics", -1)
 
 
 def test_ranking_by_lds_atomics_is_probed_and_equals_ballot_ranking(hip_lib):

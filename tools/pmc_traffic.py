@@ -52,9 +52,17 @@ ALIAS = [("rows_seg_hist_kernel", "row_partition_histogram"), ("rows_scan_kernel
          ("composite_bwd_scan_kernel", "composite_bwd"), ("composite_bwd_kernel", "composite_bwd_per_pixel"), ("composite_fwd_kernel", "composite_fwd"),
          ("preprocess_geom_kernel", "preprocess_fwd"), ("preprocess_color_kernel", "preprocess_color"), ("preprocess_fwd_kernel", "preprocess_fwd"),
          ("preprocess_bwd_kernel", "preprocess_bwd"), ("duplicate_kernel", "duplicate"),
-         ("depth_local_sort_kernel", "depth_sort_bucket_pass"), ("dls_histogram_kernel", "depth_sort_msd_histogram"), ("dls_range_kernel", "depth_sort_key_range"),
+         ("depth_local_sort_kernel", "depth_sort_bucket_pass"), ("ss_bucket_kernel", "depth_sort_bucket_pass"), ("ss_splitter_kernel", "depth_sort_sample_splitters"),
+         # (the first match wins: the scatter passes by their item count, then the histograms of the MSD and the sample depth sort by
+         # their digit rule -- the last template argument of rs_histogram_kernel -- then the other histograms by their item count)
+         # (beyond 2 M Gaussians the depth sorts run 16 items per thread too: triples -- mode 3 -- and the one-copy histogram are theirs)
+         ("rs_scatter_kernel<16, 512, 3,", "depth_sort_scatter_pass"), ("rs_scatter_kernel<16, 1024, 3,", "depth_sort_scatter_pass"),
+         ("rs_scatter_kernel<16, 256, 0,", "depth_sort_scatter_pass"),
          ("rs_scatter_kernel<16", "tile_sort_scatter_pass"), ("rs_scatter_kernel<8", "depth_sort_scatter_pass"),
-         ("rs_histogram_kernel<16", "tile_sort_histogram_pass"), ("rs_histogram_kernel<8", "depth_sort_histogram_pass"),
+         ("DigitRange<", "depth_sort_msd_histogram"), ("DigitTable<", "depth_sort_sample_histogram"),
+         # (names of kernels since folded or removed, as the profiles recorded up to round 6 spell them)
+         ("dls_histogram_kernel", "depth_sort_msd_histogram"), ("dls_range_kernel", "depth_sort_key_range"),
+         ("rs_histogram_kernel<16, 256, 1", "depth_sort_histogram_pass"), ("rs_histogram_kernel<16", "tile_sort_histogram_pass"), ("rs_histogram_kernel<8", "depth_sort_histogram_pass"),
          ("rs_scan_rows_kernel", "radix_row_scan"), ("tile_ranges_kernel", "tile_ranges"), ("scan_tiles_local_kernel", "scan_tiles"),
          ("radam_kernel", "radam"), ("l1_ssim_fwd", "l1_ssim_forward"), ("l1_ssim_bwd", "l1_ssim_backward"),
          ("l1_ssim_finish", "l1_ssim_finish"), ("attributes_fwd", "attributes_forward"), ("attributes_bwd", "attributes_backward"),

@@ -4,7 +4,7 @@
 import sqlite3
 import sys
 
-NAME_W = 160      # full template argument lists: `rs_scatter_kernel<8, 1024, 3, 10>` and `<16, 256, 2, 7>` are different kernels
+NAME_W = 160      # full template argument lists: `rs_scatter_kernel<8, 1024, 3, DigitRange<1024>>` and `<16, 256, 2, DigitBits<7>>` are different kernels
 
 
 def main(db_path, out=sys.stdout):
