@@ -171,7 +171,10 @@ PROTOTYPES = {
         _status("ex4d_attr_time_scalars", i32, f64, f64, f64, f64, i32, i32, i32, f64, P(Ex4dAttrParams)),
         _status("ex4d_attributes_forward_ex", P(Ex4dAttrParams), i32, *[vp] * 21),
         _status("ex4d_attributes_backward_ex", P(Ex4dAttrParams), i32, *[vp] * 29),
-        _status("ex4d_attributes_backward_sliced_ex", P(Ex4dAttrParams), i32, *[vp] * 28, P(i32), vp))),
+        _status("ex4d_attributes_backward_sliced_ex", P(Ex4dAttrParams), i32, *[vp] * 28, P(i32), vp),
+        _value("ex4d_motion_last_error", text),
+        _status("ex4d_motion_forward", P(Ex4dAttrParams), P(Ex4dAttrParams), i32, i32, *[vp] * 5, i32, i32, f32, vp, vp),
+        _status("ex4d_motion_backward", P(Ex4dAttrParams), P(Ex4dAttrParams), i32, i32, *[vp] * 5, i32, i32, f32, *[vp] * 5, P(i32), vp))),
     "ex4d_loss.h": ("ex4d_loss_last_error", (
         _value("ex4d_loss_last_error", text),
         _value("ex4d_l1_ssim_scratch_floats", size, i32, i32),
@@ -246,6 +249,8 @@ PROTOTYPES = {
 }
 # status function -> the *_last_error of its header
 _LAST_ERROR = {name: err for err, protos in PROTOTYPES.values() for name, _, _, is_status in protos if is_status}
+# the motion entry points are declared in ex4d_attributes.h and keep an error text of their own
+_LAST_ERROR.update({name: "ex4d_motion_last_error" for name in _LAST_ERROR if name.startswith("ex4d_motion_")})
 
 
 def exports(header):

@@ -26,6 +26,7 @@ SOURCES = {
     "ex4d_composite.hip": ["-ffp-contract=fast", "-munsafe-fp-atomics", "-fno-slp-vectorize"],
     "ex4d_api.hip": [],
     "ex4d_attributes.hip": ["-ffp-contract=off"],
+    "ex4d_motion.hip": ["-ffp-contract=off"],       # displacement between two timestamps (declared in ex4d_attributes.h): the bits of the two files above
     "ex4d_loss.hip": [],
     "ex4d_frames.hip": ["-ffp-contract=off"],       # PIL's resize (declared in ex4d_loss.h): the coefficient table's doubles must not fuse
     "ex4d_optim.hip": ["-ffp-contract=off"],

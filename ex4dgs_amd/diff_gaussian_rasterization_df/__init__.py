@@ -139,6 +139,22 @@ def current_policy():
     return _policy_stack[-1] if _policy_stack else async_frames
 
 
+_flow_expected = []
+
+
+class expect_flow:
+    """`with expect_flow(): ...` -- the caller KNOWS the dir3D of the forwards issued inside is not zero (render(..., flow_to=...)):
+    they never run on the flow-free compositing kernel, whatever an asynchronous policy has learned from the frames before."""
+
+    def __enter__(self):
+        _flow_expected.append(True)
+        return self
+
+    def __exit__(self, *exc):
+        _flow_expected.pop()
+        return False
+
+
 def _snapshot(args):
     return tuple(a.detach().cpu().clone() if isinstance(a, torch.Tensor) else a for a in args)
 
@@ -172,6 +188,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.prepared = any(ctx.needs_input_grad)
         policy = current_policy()
         capacity, no_flow = (0, False) if s.debug else policy.next_call()      # (debug synchronises after every stage)
+        no_flow = no_flow and not _flow_expected
         native_fwd = lambda *a: _C.rasterize_gaussians(*a, prepare_backward=ctx.prepared, instance_capacity=capacity, assume_no_flow=no_flow)
         (num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer, depth, acc, flow, idxs) = _call_native(
             native_fwd, args, s.debug, "snapshot_fw.dump", "forward")

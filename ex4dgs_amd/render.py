@@ -8,12 +8,13 @@ zero `screenspace_points` and `flow` grad-trap tensors that retain their gradien
 subpixel_offset[H,W,2], prefiltered=False, min_depth/max_depth = near/far, shs (not colors_precomp),
 scales/rotations (not cov3D_precomp).
 """
+import contextlib
 import math
 from types import SimpleNamespace
 
 import torch
 
-from .diff_gaussian_rasterization_df import GaussianRasterizationSettings, GaussianRasterizer
+from .diff_gaussian_rasterization_df import GaussianRasterizationSettings, GaussianRasterizer, expect_flow
 
 DEFAULT_PIPE = SimpleNamespace(convert_SHs_python=False, compute_cov3D_python=False, debug=False)
 
@@ -31,7 +32,14 @@ def _zero_offsets(H, W, device):
 
 
 def render(viewpoint_camera, pc, pipe, bg_color, timestamp=None, scaling_modifier=1.0, override_color=None,
-           subpixel_offset=None, mode=0, training=False, near=0.2, far=100.0, sync=True):
+           subpixel_offset=None, mode=0, training=False, near=0.2, far=100.0, sync=True, flow_to=None):
+    """flow_to: None (default) feeds the rasterizer a zero dir3D, the gradient trap of the `l1_accum` error hook, as the reference
+    does: "opticalflow" is then a zero image.  A timestamp makes dir3D the screen displacement of every Gaussian from `timestamp` to
+    `flow_to` for this camera and `near` (pc.get_displacement(..., space="screen")): "opticalflow" is the rendered motion in pixels
+    (and view depth in the third channel) per (flow_to - timestamp), normalised by the accumulated alpha and zero where nothing was
+    hit; "viewspace_l1points" is that displacement tensor, and with autograd on a loss on "opticalflow" reaches `_xyz`, `_xyz_disp`
+    and `_xyz_motion`.  The `l1_accum` hook and `flow_to` use the same channel: they exclude each other (with `flow_to`,
+    viewspace_l1points.grad is dL/d(displacement), not the accumulated L1 error)."""
     pipe = DEFAULT_PIPE if pipe is None else pipe
     if getattr(pipe, "compute_cov3D_python", False) or getattr(pipe, "convert_SHs_python", False):
         # gaussian_renderer/__init__.py:76-78, :87-93: the reference's Python-side covariance / SH evaluation bypasses the kernels
@@ -50,7 +58,12 @@ def render(viewpoint_camera, pc, pipe, bg_color, timestamp=None, scaling_modifie
     # read by the rasterizer (only dir3D's are: it is composited into the flow image), so that one need not even be filled.
     track = torch.is_grad_enabled()
     screenspace_points = torch.empty_like(means3D, requires_grad=track)
-    flow = torch.zeros_like(means3D, requires_grad=track)
+    if flow_to is None:
+        flow = torch.zeros_like(means3D, requires_grad=track)
+    else:
+        flow = pc.get_displacement(timestamp, flow_to, mode=mode, space="screen", camera=viewpoint_camera, near=near)
+        if flow.requires_grad:
+            flow.retain_grad()
 
     H, W = int(viewpoint_camera.image_height), int(viewpoint_camera.image_width)
     if subpixel_offset is None:
@@ -69,9 +82,11 @@ def render(viewpoint_camera, pc, pipe, bg_color, timestamp=None, scaling_modifie
     rotations = pc.get_rotation_at_t(timestamp, mode=mode)
     shs, colors_precomp = (pc.get_features(mode=mode), None) if override_color is None else (None, override_color)
 
-    rendered_image, radii, rendered_depth, out_flow, acc, idxs = rasterizer(
-        means3D=means3D, means2D=screenspace_points, dir3D=flow, shs=shs, colors_precomp=colors_precomp,
-        opacities=opacity, scales=scales, rotations=rotations, cov3D_precomp=None)
+    # a flow_to frame never runs on the flow-free compositing kernel an asynchronous policy may have learned from plain frames
+    with (contextlib.nullcontext() if flow_to is None else expect_flow()):
+        rendered_image, radii, rendered_depth, out_flow, acc, idxs = rasterizer(
+            means3D=means3D, means2D=screenspace_points, dir3D=flow, shs=shs, colors_precomp=colors_precomp,
+            opacities=opacity, scales=scales, rotations=rotations, cov3D_precomp=None)
     if sync and means3D.is_cuda:
         torch.cuda.synchronize()        # gaussian_renderer/__init__.py:111
     return {"render": rendered_image, "depth": rendered_depth, "opticalflow": out_flow, "acc": acc,

@@ -254,6 +254,16 @@ class DynamicGaussians:
             dyn = hermite(y[:, k - 1, :3], y[:, k, :3], y[:, k + 1, :3], y[:, k + 2, :3], d)
         return dyn if mode == 2 else torch.cat([static, dyn], dim=0).contiguous()
 
+    def get_displacement(self, t0, t1, mode=0, space="world", camera=None, near=0.2):
+        """Where every Gaussian goes between t0 and t1 (ex4dgs_amd.motion.displacement with the model's interpolator and time
+        numbers): [N,3], x(t1) - x(t0) in the world, or (du, dv, dz) in pixels and view depth for `camera` with space='screen'
+        (exact zeros for rows at or behind `near` at either timestamp).  Rows by `mode` as in get_xyz_at_t.  HIP only."""
+        from .motion import displacement
+        out = displacement({n: getattr(self, n) for n in ("_xyz", "_xyz_disp", "_xyz_motion")}, t0, t1, space=space, camera=camera,
+                           near=near, interp_type=self.interp_type, duration=self.duration, interval=self.interval,
+                           time_shift=self.time_shift, var_pad=self.var_pad)
+        return self._rows(out, mode)
+
     def get_rotation_at_t(self, t, mode=0):
         if self.fused:
             return self._rows(self.evaluate_at_t(t)[1], mode)

@@ -121,6 +121,44 @@ int ex4d_attributes_backward_sliced_ex(const Ex4dAttrParams *a, int32_t interp, 
     float *g_opacity_duration_var, float *g_scaling_motion, float *g_features_dc_motion, float *g_features_rest_motion,
     int32_t *slices, void *stream);
 
+/* ---- Motion: the displacement of every Gaussian between two timestamps t0 and t1 (ex4d_motion.hip).
+ *
+ * a0, a1 are the scalars of t0 and t1 (ex4d_attr_time_scalars, same model); only the position tensors are read.
+ *   EX4D_MOTION_WORLD   out = x(t1) - x(t0), one float32 subtraction per component; x(t) is exactly the float32 value
+ *                       ex4d_attributes_forward_ex writes to means3D for that timestamp (its position arithmetic is restated).
+ *   EX4D_MOTION_SCREEN  out = (u1 - u0, v1 - v0, z1 - z0): (u, v) is the pixel position the rasterizer's preprocess computes for that
+ *                       mean (full projection, inv_w = 1 / (w + 1e-7f), ndc2Pix in double), z its view depth -- the bits the geometry
+ *                       records hold.  Needs viewmatrix[16], projmatrix[16] (device, column-major as the rasterizer takes them), W, H.
+ *                       A row whose view depth is <= min_depth at either timestamp gets exactly (0, 0, 0) and zero gradients; no other
+ *                       culling (the rasterizer culls by the frame it renders).  Units: pixels and scene depth per (t1 - t0): fed
+ *                       to the rasterizer as dir3D, out_flow is the optical flow in pixels.
+ * out is [Ns+Nd,3], static rows first, every row written (callers may pass uninitialised memory).  One launch, no atomics, no host
+ * read-back: graph-capturable.  Ns == 0 or Nd == 0 is legal.
+ *
+ * Refused with EX4D_ERR_ARG before anything is launched (text: ex4d_motion_last_error): an unknown interpolator or space, a keyframe
+ * index outside the interpolator's valid range at either timestamp, a0 and a1 that disagree in Ns, Nd or K, screen space without
+ * matrices or image size. */
+enum { EX4D_MOTION_WORLD = 0, EX4D_MOTION_SCREEN = 1 };
+
+const char *ex4d_motion_last_error(void);
+
+int ex4d_motion_forward(const Ex4dAttrParams *a0, const Ex4dAttrParams *a1, int32_t interp, int32_t space,
+    const float *xyz /*[Ns,3]*/, const float *xyz_disp /*[Ns,3]*/, const float *xyz_motion /*[Nd,K,3]*/,
+    const float *viewmatrix, const float *projmatrix, int32_t W, int32_t H, float min_depth,
+    float *out /*[Ns+Nd,3]*/, void *stream);
+
+/* Backward of the above for g_out[Ns+Nd,3].  g_xyz[Ns,3] and g_xyz_disp[Ns,3] are fully written (world space: g_xyz is exact zeros).
+ * The keyframe gradient comes as TWO WINDOWS, without a dense zero fill: g_win0 holds the gradients of keyframes windows[0] ..
+ * windows[0]+windows[1]-1 that flow through x(t0), g_win1 those of windows[2] .. through x(t1); each is [Nd,4,3] ([Nd,2,3] under
+ * linear) and fully written.  windows = int32[4] {first0, count, first1, count}, written on the host: {k0-1, 4, k1-1, 4}, linear
+ * {k0, 2, k1, 2} -- the form ex4d_radam_step_sliced takes as two windows of one tensor.  The dense gradient is window 0 plus
+ * window 1, summed in that order where they overlap.  The adjoints are those of ex4d_attributes_backward_ex (pchip: NaN on the
+ * keyframes the quotient touches where y[k+1] == y[k-1], as there). */
+int ex4d_motion_backward(const Ex4dAttrParams *a0, const Ex4dAttrParams *a1, int32_t interp, int32_t space,
+    const float *xyz, const float *xyz_disp, const float *xyz_motion,
+    const float *viewmatrix, const float *projmatrix, int32_t W, int32_t H, float min_depth,
+    const float *g_out, float *g_xyz, float *g_xyz_disp, float *g_win0, float *g_win1, int32_t *windows, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
