@@ -189,6 +189,9 @@ PROTOTYPES = {
         _status("ex4d_resize_u8_table", i32, i32, i32, vp),
         _value("ex4d_resize_u8_scratch_bytes", size, i32, i32, i32, i32),
         _status("ex4d_resize_u8", i32, i32, i32, i32, i32, *[vp] * 6),
+        _value("ex4d_flow_loss_scratch_floats", size, i32, i32),
+        _status("ex4d_flow_loss_forward", i32, i32, vp, vp, i32, f32, vp, i32, f32, *[vp] * 4),
+        _status("ex4d_flow_loss_backward", i32, i32, vp, vp, i32, f32, vp, i32, f32, *[vp] * 4),
         _value("ex4d_frame_skssim_scratch_floats", size, i32, i32),
         _status("ex4d_frame_skssim", i32, i32, vp, vp, i32, *[vp] * 3),
         _status("ex4d_frame_skssim_u8", i32, i32, vp, vp, i32, vp, i32, *[vp] * 3))),

@@ -29,6 +29,7 @@ SOURCES = {
     "ex4d_motion.hip": ["-ffp-contract=off"],       # displacement between two timestamps (declared in ex4d_attributes.h): the bits of the two files above
     "ex4d_loss.hip": [],
     "ex4d_frames.hip": ["-ffp-contract=off"],       # PIL's resize (declared in ex4d_loss.h): the coefficient table's doubles must not fuse
+    "ex4d_flow.hip": ["-ffp-contract=off"],         # flow loss on 16-bit ground truth (declared in ex4d_loss.h): the decode gives the reference's bits
     "ex4d_optim.hip": ["-ffp-contract=off"],
     "ex4d_knn.hip": ["-ffp-contract=off"],
     "ex4d_densify.hip": ["-ffp-contract=off"],      # density control: threshold decisions and copied values follow torch's float32 ops

@@ -13,6 +13,7 @@ rasterization of frame i+1; with one (the default of the multi-GPU bench) it has
 i+1 and is exposed except for the part beside the attribute backward.
 No CPU fallback: everything here needs the HIP library and a ROCm device.
 """
+import contextlib
 import math
 
 import torch
@@ -81,6 +82,7 @@ class FrameTrainer:
         per view.  exchange="allreduce" without a process group of several ranks (and without force_collectives) would train with no
         exchange at all: with regularizers that request is still refused (NotImplementedError); ask for exchange="none"."""
         assert exchange in ("none", "allreduce", "sharded")
+        self._exchange_asked = exchange
         self.k = int(views_per_step)
         assert self.k >= 1
         if self.k > 1:
@@ -153,6 +155,7 @@ class FrameTrainer:
         self.async_forward = False if async_forward is None else bool(async_forward)
         self.replays = 0
         self._frame = self._last_args = None
+        self._flow = None
         if self.async_forward:
             if self.mode != "none":
                 raise ValueError("async_forward re-runs an overflowing frame on its own: single rank, exchange 'none' only")
@@ -235,17 +238,29 @@ class FrameTrainer:
                 n += sum(ex.bytes_on_wire() for ex in self.opt.row_exchange.values())
         return n
 
-    def step(self, cam, bg, t, upstream, near=0.2, far=300.0):
+    def step(self, cam, bg, t, upstream, near=0.2, far=300.0, flow_to=None):
         """upstream: callable(render dict) -> (list of outputs, list of their gradients), e.g. a loss evaluated with the fused
-        L1+SSIM op, or fixed synthetic gradients.  Returns the render dict (tensors of this frame, detached)."""
+        L1+SSIM op, or fixed synthetic gradients.  Returns the render dict (tensors of this frame, detached).
+        flow_to (default None: a zero dir3D, the step as it always was): a timestamp makes dir3D the screen displacement of every
+        Gaussian from t to flow_to for this camera and `near` (motion.displacement_raw), so out["opticalflow"] is the rendered motion in
+        pixels and an upstream loss on it (flow.flow_loss) trains `_xyz`, `_xyz_disp` and `_xyz_motion`: dir3D's gradient goes through
+        motion.displacement_backward_raw, its two static gradients are added to the attribute backward's, and `_xyz_motion` takes
+        three gradient windows in the order attribute window, motion window 0, motion window 1 -- handed to ex4d_radam_step_sliced as
+        they are, or added into the dense gradient in that order.  One rank, one view per step: exchange "none" only."""
+        if flow_to is not None:
+            if self._exchange_asked != "none":
+                raise NotImplementedError(f"flow_to on a FrameTrainer with exchange='{self._exchange_asked}': the motion windows of a flow step are "
+                                          "not exchanged between ranks; exchange='none' only")
+            if self.k != 1:
+                raise NotImplementedError(f"flow_to with views_per_step={self.k}: a flow step takes one view per optimizer step")
         # the previous frame's exchange must be complete before this frame's optimizer-updated parameters are read (optimizer on) --
         # without an optimizer it only has to finish before its buffers are overwritten by this frame's attribute backward
         if self.optimizer and self._grads is not None:
             self._apply_optimizer()
         elif self.async_forward:
             self._settle_frame()
-        self._last_args = (cam, bg, t, upstream, near, far)
-        return self._run_frame(cam, bg, t, upstream, near, far)
+        self._last_args = (cam, bg, t, upstream, near, far, flow_to)
+        return self._run_frame(cam, bg, t, upstream, near, far, flow_to)
 
     def _settle_frame(self):
         """async_forward: the pending frame's status; a frame whose tile lists were truncated is run again (with the capacity the policy
@@ -265,7 +280,7 @@ class FrameTrainer:
             self.replays += 1
             self._run_frame(*self._last_args)       # leaves the re-run's pending status in self._frame: validated by the next turn of the loop
 
-    def _run_frame(self, cam, bg, t, upstream, near, far):
+    def _run_frame(self, cam, bg, t, upstream, near, far, flow_to=None):
         m = self.model
         main = torch.cuda.current_stream(self.device)
         scal = attr.time_scalars(t, m.num_static, m.num_dynamic, m._xyz_motion.shape[1] if m.num_dynamic else 0,
@@ -275,26 +290,40 @@ class FrameTrainer:
         leaves = [x.requires_grad_(True) for x in (xyz, rot, opa, scl)]
         feats = [self.params[i].detach().requires_grad_(True) for i in self.feature_idx]
         means2D = torch.empty_like(xyz, requires_grad=True)
-        dir3D = torch.zeros_like(xyz, requires_grad=True)
+        if flow_to is None:
+            dir3D = torch.zeros_like(xyz, requires_grad=True)
+            flow_ctx = contextlib.nullcontext()
+        else:
+            from . import motion
+            from .diff_gaussian_rasterization_df import expect_flow
+            scal_to = attr.time_scalars(flow_to, m.num_static, m.num_dynamic, m._xyz_motion.shape[1] if m.num_dynamic else 0,
+                                        m.duration, m.interval, m.time_shift, m.var_pad, self.interp_type)
+            moving = [self.params[self.names.index(n)] for n in motion.PARAM_NAMES]
+            with torch.no_grad():
+                dir3D = motion.displacement_raw(scal, scal_to, *moving, space="screen", camera=cam, near=near, interp_type=self.interp_type)
+            dir3D.requires_grad_(True)
+            flow_ctx = expect_flow()        # never the flow-free compositing kernel an asynchronous policy learned from plain frames
         e = torch.Tensor([])
         st = self._settings(cam, bg, near, far)
         if self.async_forward:
             from .diff_gaussian_rasterization_df import use_policy
-            with use_policy(self._policy):
+            with use_policy(self._policy), flow_ctx:
                 color, radii, depth, flow, acc, idx = rasterize_gaussians(leaves[0], means2D, dir3D, SplitSH(*feats), e, leaves[2], leaves[3], leaves[1], e, st)
             self._frame = self._policy.pending[-1] if self._policy.pending else None      # (None: the policy's synchronous seed frame)
         else:
-            color, radii, depth, flow, acc, idx = rasterize_gaussians(leaves[0], means2D, dir3D, SplitSH(*feats), e, leaves[2], leaves[3], leaves[1], e, st)
+            with flow_ctx:
+                color, radii, depth, flow, acc, idx = rasterize_gaussians(leaves[0], means2D, dir3D, SplitSH(*feats), e, leaves[2], leaves[3], leaves[1], e, st)
         out = {"render": color, "depth": depth, "opticalflow": flow, "acc": acc, "radii": radii, "dominent_idxs": idx,
                "viewspace_points": means2D, "viewspace_l1points": dir3D, "visibility_filter": radii > 0}
         outs, gouts = upstream(out)
         torch.autograd.backward(outs, gouts)
         gin = [x.grad for x in leaves]                    # dL/d(means3D, rotations, opacities, scales)
         fgrads = [f.grad for f in feats]
+        gdir = None if flow_to is None else (dir3D.grad if dir3D.grad is not None else torch.zeros_like(dir3D))
         # ---- attribute backward + exchange: side stream, overlapping the next frame's rasterization
         if self.side is not None:
             self.side.wait_stream(main)
-            for g in gin + fgrads:
+            for g in gin + fgrads + ([] if gdir is None else [gdir]):
                 g.record_stream(self.side)
             ctx = torch.cuda.stream(self.side)
         else:
@@ -309,6 +338,9 @@ class FrameTrainer:
                 gth.wait()
             gout = attr.backward_raw(scal, self.params, (gin[0], gin[1], gin[2], gin[3], None), with_shs=False, out=self.pgrad, sliced=self.sliced,
                                      interp_type=self.interp_type)
+            self._flow = None
+            if gdir is not None:
+                self._flow_backward(scal, scal_to, moving, gdir, cam, near, gout[0] if self.sliced else gout, main)
             windows = None
             if self.sliced:
                 gout, hint = gout
@@ -323,6 +355,28 @@ class FrameTrainer:
         if pending:
             self._note_regularizers()
         return out
+
+    def _flow_backward(self, scal, scal_to, moving, gdir, cam, near, gout, main):
+        """dL/d(dir3D) of a flow_to frame back to `_xyz`, `_xyz_disp` and `_xyz_motion` (on the attribute backward's stream, after it):
+        the two static gradients are added to the attribute backward's; the two keyframe windows wait for the optimizer step (sliced:
+        self._flow, two more windows of `_xyz_motion`) or are added into the dense gradient, window 0 first."""
+        from . import motion
+        g_xyz, g_disp, g_win0, g_win1, mhint = motion.displacement_backward_raw(scal, scal_to, *moving, gdir, space="screen", camera=cam, near=near,
+                                                                                interp_type=self.interp_type)
+        ix, idisp, imot = (self.names.index(n) for n in motion.PARAM_NAMES)
+        if gout[ix].numel():
+            gout[ix].add_(g_xyz)
+            gout[idisp].add_(g_disp)
+        if not g_win0.shape[0]:
+            return
+        if self.sliced:
+            for w in (g_win0, g_win1):
+                w.record_stream(main)                    # consumed by the optimizer step on the caller's stream
+            self._flow = (g_win0, g_win1, mhint)
+        else:
+            first0, count0, first1, count1 = mhint
+            gout[imot][:, first0:first0 + count0] += g_win0
+            gout[imot][:, first1:first1 + count1] += g_win1
 
     def _submit(self, grads, windows=None):
         """A view's 15 gradients on their way to the optimizer step: added to the group's accumulators (views_per_step > 1) and, with
@@ -411,8 +465,12 @@ class FrameTrainer:
                 for gth, i in zip(self.kf_gather, self.kf_idx):
                     p = self.params[i]
                     count, Cc = self.sliced_shapes[self.names[i]]
+                    wins = gth.windows(count)
+                    if self._flow is not None and self.names[i] == "_xyz_motion":
+                        g_win0, g_win1, mhint = self._flow   # a flow_to frame: attribute window, motion window 0, motion window 1, summed in that order
+                        wins = wins + [(mhint[0], mhint[1], g_win0.data_ptr()), (mhint[2], mhint[3], g_win1.data_ptr())]
                     item = (p.data_ptr(), self.m[i].data_ptr(), self.v[i].data_ptr(), p.shape[0], p.shape[1], Cc, self.lrs[i], self.steps,
-                            gth.windows(count), gth.first_device_ptr())
+                            wins, gth.first_device_ptr())
                     if w is not None:
                         motion = self.names[i] == "_xyz_motion"
                         item += (REG_MOTION if motion else REG_ROT, w[1] if motion else w[2], p.shape[0])

@@ -115,6 +115,47 @@ size_t ex4d_resize_u8_scratch_bytes(int32_t H_in, int32_t W_in, int32_t H_out, i
 int ex4d_resize_u8(int32_t H_in, int32_t W_in, int32_t H_out, int32_t W_out, int32_t pixel_stride, const uint8_t *src, uint8_t *dst,
                    const int32_t *table_x /* device */, const int32_t *table_y /* device */, uint8_t *scratch, void *stream);
 
+/* FLOW: supervising the rendered motion (render(..., flow_to=t1): the rasterizer's `opticalflow` output in pixels) with the ground
+ * truth the reference's data layer carries (utils/general_utils.py:39-53 read_opticalflow / decode_flow, scene/cameras.py:85,102
+ * opticalflow_path): a 16-bit three-channel image, decoded on load.
+ *   flow  DEVICE float32 [3,H,W]: u, v, depth change.  The third plane is never read.
+ *   gt    DEVICE uint16 [H,W,S], pixel_stride S = 3 or 4 words per pixel, at any 2-byte alignment (hence void *); word 0 = u, word 1 = v,
+ *         word 2 = validity, as decode_flow indexes them; a fourth word is never read.
+ *   acc   DEVICE float32 [H,W] (the rasterizer's accumulated alpha) or NULL: a per-pixel weight, a constant with no gradient.
+ * Decode, the bits of the reference's float32 arithmetic (one rounding: the subtraction and the division are exact):
+ *     g = (float)(code - 32768) / 256 * flow_scale,     m = code2 > 32768
+ * flow_scale carries read_opticalflow's resolution[1] / rows; the encoded frame is at render resolution (cv2's INTER_AREA resize of
+ * encoded flow is not offered).  Loss, this library's definition, float32 per pixel:
+ *     r = (flow_u - g_u, flow_v - g_v)
+ *     rho = |r_u| + |r_v|  (EX4D_FLOW_L1)   or   sqrt(r_u^2 + r_v^2 + eps^2)  (EX4D_FLOW_CHARBONNIER; eps finite and > 0)
+ *     loss = sum m w rho / max(sum m, 1),   w = acc[p] or 1
+ * Invalid pixels are selected out: nothing behind them, a NaN included, reaches a sum or a gradient.  A NaN in a VALID rendered pixel
+ * propagates into the loss.
+ * Forward: loss DEVICE float[1]; row DEVICE double[4], all four written on every call:
+ *     row[0] the loss   row[1] number of valid pixels (exact)   row[2] mean end-point error sqrt(r_u^2 + r_v^2) over the valid pixels,
+ *     unweighted, 0 when there are none   row[3] number of valid pixels whose rendered u or v is not finite (exact)
+ * The sums are float per workgroup and double across workgroups, in a fixed order: equal inputs give equal bits.
+ * scratch: ex4d_flow_loss_scratch_floats(H, W) floats (0 for a refused size).
+ * Backward: grad_flow DEVICE [3,H,W], fully written: planes 0 and 1 grad_loss[0] * m w / max(count, 1) * d rho / d r -- sign(r) with
+ * sign(0) = 0 for L1, r / rho for Charbonnier -- and exact zeros in plane 2, at every invalid pixel, and everywhere when no pixel is
+ * valid.  row: the forward's row of the same inputs (its count is read on the device); grad_loss DEVICE float[1].
+ * Refused before any launch, with a message: H or W <= 0, a stride other than 3 or 4, an unknown kind, Charbonnier with eps <= 0 or
+ * not finite, a NULL required pointer.  No allocation, no copy, no synchronisation, no atomics: the calls can be captured into a graph.
+ * Tiling: a lane owns EX4D_FLOW_PIXELS_PER_LANE consecutive pixels of the flat [H W] index, a workgroup has EX4D_FLOW_THREADS lanes, and
+ * the one wave that adds the workgroups' partial sums takes EX4D_FLOW_FOLD of them per step. */
+#define EX4D_FLOW_L1 0
+#define EX4D_FLOW_CHARBONNIER 1
+#define EX4D_FLOW_PIXELS_PER_LANE 4
+#define EX4D_FLOW_THREADS 256
+#define EX4D_FLOW_FOLD 64
+size_t ex4d_flow_loss_scratch_floats(int32_t H, int32_t W);
+int ex4d_flow_loss_forward(int32_t H, int32_t W, const float *flow, const void *gt, int32_t pixel_stride, float flow_scale,
+                           const float *acc, int32_t kind, float eps, float *loss, double *row /* device [4] */, float *scratch,
+                           void *stream);
+int ex4d_flow_loss_backward(int32_t H, int32_t W, const float *flow, const void *gt, int32_t pixel_stride, float flow_scale,
+                            const float *acc, int32_t kind, float eps, const double *row /* device [4] */,
+                            const float *grad_loss /* device [1] */, float *grad_flow, void *stream);
+
 /* scikit-image's SSIM of a rendered view: the SKSSIM and SKSSIM2 entries of render.py:78-79,
  *     sk_ssim(render, gt, data_range=R, multichannel=True, channel_axis=0)   with R = 1 and R = 2,
  * as scikit-image 0.22 and later read that call (multichannel is ignored, channel_axis=0 holds; earlier releases fail on a [3,H,W]
