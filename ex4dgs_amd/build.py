@@ -26,7 +26,7 @@ SOURCES = {
     "ex4d_composite.hip": ["-ffp-contract=fast", "-munsafe-fp-atomics", "-fno-slp-vectorize"],
     "ex4d_api.hip": [],
     "ex4d_attributes.hip": ["-ffp-contract=off"],
-    "ex4d_motion.hip": ["-ffp-contract=off"],       # displacement between two timestamps (declared in ex4d_attributes.h): the bits of the two files above
+    "ex4d_motion.hip": ["-ffp-contract=off"],       # displacement between two timestamps (declared in ex4d_attributes.h): ex4d_keyframes.h / ex4d_camera.h give it the bits of the two files above
     "ex4d_loss.hip": [],
     "ex4d_frames.hip": ["-ffp-contract=off"],       # PIL's resize (declared in ex4d_loss.h): the coefficient table's doubles must not fuse
     "ex4d_flow.hip": ["-ffp-contract=off"],         # flow loss on 16-bit ground truth (declared in ex4d_loss.h): the decode gives the reference's bits
@@ -124,7 +124,7 @@ def build(force=False, verbose=False, extra_flags=()):
     headers = [os.path.join(CSRC, "ex4d_internal.h"), os.path.join(HERE, "..", "include", "ex4d_rasterizer.h"),
                os.path.join(HERE, "..", "include", "ex4d_attributes.h"), os.path.join(HERE, "..", "include", "ex4d_loss.h"), os.path.join(HERE, "..", "include", "ex4d_optim.h"), os.path.join(HERE, "..", "include", "ex4d_knn.h"), os.path.join(HERE, "..", "include", "ex4d_trainer.h"),
                os.path.join(HERE, "..", "include", "ex4d_densify.h"), os.path.join(HERE, "..", "include", "ex4d_regularizers.h"),
-               os.path.join(CSRC, "ex4d_reg_rows.h"),
+               os.path.join(CSRC, "ex4d_reg_rows.h"), os.path.join(CSRC, "ex4d_keyframes.h"), os.path.join(CSRC, "ex4d_camera.h"),
                os.path.abspath(__file__)]
     objs = []
     for src, flags in SOURCES.items():

@@ -9,8 +9,10 @@
 // and their autograd backward, by two streaming kernels each way: one thread per Gaussian for the 11 floats of
 // (xyz, rotation, opacity, scale), one grid-stride element-wise kernel for the [N,16,3] SH block (the only large
 // stream: 192 B per Gaussian each way).  Static rows first, then dynamic rows (c_gaussian_model.py:193).
-// Compiled with -ffp-contract=off: same float32 operation order as the reference's tensor arithmetic.
+// Compiled with -ffp-contract=off: same float32 operation order as the reference's tensor arithmetic.  The position arithmetic
+// (x(t) and its adjoint) lives in ex4d_keyframes.h, shared with ex4d_motion.hip.
 #include "ex4d_internal.h"
+#include "ex4d_keyframes.h"
 #include <cmath>
 #include <cstdio>
 
@@ -106,29 +108,6 @@ __device__ __forceinline__ void bigaussian_forward(float c0, float c1, float v0,
     b.out = b.inside ? 1.0f : b.o;
 }
 
-// One component of the monotone Hermite slopes (utils/interpolations.py:72-73): a = y[k+1]-y[k], b = y[k]-y[k-1], s = y[k+1]-y[k-1], each
-// its own subtraction; m = a*b > 0 ? (a*b)/s*2 : 0.  The quotient is formed (and, in the adjoint, differentiated) whether kept or not.
-struct PchipSlope { float a, b, s, p; bool keep; };
-
-__device__ __forceinline__ float pchip_slope(float ym, float y0, float yp, PchipSlope &m)
-{
-    m.a = yp - y0; m.b = y0 - ym; m.s = yp - ym;
-    m.p = m.a * m.b;
-    m.keep = m.p > 0.f;
-    const float q = m.p / m.s * 2.0f;
-    return m.keep ? q : 0.f;
-}
-
-// what autograd hands back through where / *2 / div / mul for a slope gradient g_m: the gradients of a, b and s
-__device__ __forceinline__ void pchip_slope_adjoint(const PchipSlope &m, float g_m, float &g_a, float &g_b, float &g_s)
-{
-    const float g_q = (m.keep ? g_m : 0.f) * 2.0f;
-    const float g_p = g_q / m.s;
-    g_s = -g_q * ((m.p / m.s) / m.s);
-    g_a = g_p * m.b;
-    g_b = g_p * m.a;
-}
-
 template <int INTERP>
 __global__ __launch_bounds__(256) void attributes_fwd_kernel(Ex4dAttrParams a,
     const float *__restrict__ xyz, const float *__restrict__ xyz_disp, const float *__restrict__ rotation,
@@ -143,8 +122,7 @@ __global__ __launch_bounds__(256) void attributes_fwd_kernel(Ex4dAttrParams a,
     float m[3], q[4], op, sc[3];
     if (i < a.Ns) {
         // c_gaussian_model.py:180, :198, :357, :335
-#pragma unroll
-        for (int c = 0; c < 3; c++) m[c] = xyz[3 * (size_t)i + c] + (xyz_disp[3 * (size_t)i + c] * a.t) / a.duration;
+        static_position(a, i, xyz, xyz_disp, m);
         const float4 r = reinterpret_cast<const float4 *>(rotation)[i];
         q[0] = r.x; q[1] = r.y; q[2] = r.z; q[3] = r.w;
         op = sigmoidf_(opacity[i]);
@@ -152,28 +130,7 @@ __global__ __launch_bounds__(256) void attributes_fwd_kernel(Ex4dAttrParams a,
         for (int c = 0; c < 3; c++) sc[c] = expf(scaling[3 * (size_t)i + c]);
     } else {
         const size_t j = (size_t)(i - a.Ns);
-        if (INTERP == EX4D_INTERP_LINEAR) {
-            // keyframes k, k+1 with the weights 1-delta, delta (interpolations.py:6-7, c_gaussian_model.py:107)
-            const float *y = xyz_motion + (j * a.K + a.k) * 3;
-#pragma unroll
-            for (int c = 0; c < 3; c++) m[c] = y[c] * a.h00 + y[3 + c] * a.h01;
-        } else {
-            // Hermite over keyframes k-1..k+2: Catmull-Rom slopes (interpolations.py:81-93, c_gaussian_model.py:118) or the monotone
-            // ones of pchip (interpolations.py:65-77, c_gaussian_model.py:143)
-            const float *y = xyz_motion + (j * a.K + (a.k - 1)) * 3;
-#pragma unroll
-            for (int c = 0; c < 3; c++) {
-                const float y0 = y[c], y1 = y[3 + c], y2 = y[6 + c], y3 = y[9 + c];
-                float mk, mk1;
-                if (INTERP == EX4D_INTERP_PCHIP) {
-                    PchipSlope s0, s1;
-                    mk = pchip_slope(y0, y1, y2, s0); mk1 = pchip_slope(y1, y2, y3, s1);
-                } else {
-                    mk = (y2 - y0) / 2.0f; mk1 = (y3 - y1) / 2.0f;
-                }
-                m[c] = a.h00 * y1 + a.h10 * mk + a.h01 * y2 + a.h11 * mk1;
-            }
-        }
+        keyframe_position<INTERP>(a, j, xyz_motion, m);
         const float4 *rq = reinterpret_cast<const float4 *>(rotation_motion) + j * a.K + a.k;
         const float4 r1 = rq[0], r2 = rq[1];
         const float q1[4] = { r1.x, r1.y, r1.z, r1.w }, q2[4] = { r2.x, r2.y, r2.z, r2.w };
@@ -250,11 +207,12 @@ __global__ __launch_bounds__(256) void attributes_bwd_kernel(Ex4dAttrParams a,
         // the weights back onto the keyframes of the window (the other slices were zero-filled by the host memset)
         // sliced: g_xyz_motion is [Nd,4,3] (keyframes k-1..k+2; linear: [Nd,2,3], keyframes k, k+1), g_rotation_motion [Nd,2,4]
         // (keyframes k, k+1): nothing else exists
-        if (INTERP == EX4D_INTERP_LINEAR) {
-            float *gy = g_xyz_motion + (sliced ? j * 6 : (j * a.K + a.k) * 3);
-#pragma unroll
-            for (int c = 0; c < 3; c++) { gy[c] = gm[c] * a.h00; gy[3 + c] = gm[c] * a.h01; }
-        } else if (INTERP == EX4D_INTERP_PCHIP) {
+        constexpr int WIN = ex4d_key_window(INTERP, 0).count * 3;
+        if (INTERP == EX4D_INTERP_PCHIP) {
+            // MIRRORS the pchip branch of keyframe_position_adjoint (ex4d_keyframes.h), statement for statement: through the shared function
+            // this one instantiation compiles to other machine code (a branch on `sliced`, 14 more instructions, 2 more VGPRs, the
+            // floating-point instructions in another order: DESIGN.md, "Keyframe interpolation").  tests/test_gpu_motion.py holds the two
+            // to the same bits.
             const float *y = xyz_motion + (j * a.K + (a.k - 1)) * 3;
             float *gy = g_xyz_motion + (sliced ? j * 12 : (j * a.K + (a.k - 1)) * 3);
 #pragma unroll
@@ -265,21 +223,14 @@ __global__ __launch_bounds__(256) void attributes_bwd_kernel(Ex4dAttrParams a,
                 float ga0, gb0, gs0, ga1, gb1, gs1;
                 pchip_slope_adjoint(s0, a.h10 * gm[c], ga0, gb0, gs0);
                 pchip_slope_adjoint(s1, a.h11 * gm[c], ga1, gb1, gs1);
-                // a = y[k+1]-y[k], b = y[k]-y[k-1], s = y[k+1]-y[k-1] of m_k; the same one keyframe on for m_{k+1}
                 gy[c] = -gb0 - gs0;
                 gy[3 + c] = a.h00 * gm[c] + (gb0 - ga0) + (-gb1 - gs1);
                 gy[6 + c] = a.h01 * gm[c] + (ga0 + gs0) + (gb1 - ga1);
                 gy[9 + c] = ga1 + gs1;
             }
         } else {
-            float *gy = g_xyz_motion + (sliced ? j * 12 : (j * a.K + (a.k - 1)) * 3);
-#pragma unroll
-            for (int c = 0; c < 3; c++) {
-                gy[c] = -(a.h10 * gm[c]) / 2.0f;
-                gy[3 + c] = a.h00 * gm[c] - (a.h11 * gm[c]) / 2.0f;
-                gy[6 + c] = (a.h10 * gm[c]) / 2.0f + a.h01 * gm[c];
-                gy[9 + c] = (a.h11 * gm[c]) / 2.0f;
-            }
+            float *gy = g_xyz_motion + (sliced ? j * WIN : (j * a.K + ex4d_key_window(INTERP, a.k).first) * 3);
+            keyframe_position_adjoint<INTERP>(a, j, xyz_motion, gm, gy);
         }
         const float4 *rq = reinterpret_cast<const float4 *>(rotation_motion) + j * a.K + a.k;
         const float4 r1 = rq[0], r2 = rq[1];
@@ -314,20 +265,11 @@ __global__ __launch_bounds__(256) void attributes_bwd_kernel(Ex4dAttrParams a,
 
 thread_local char g_attr_err[256] = "";
 
-// keyframes the position interpolator reads: k .. k+1 (linear) or k-1 .. k+2 (cube, pchip); the slerp's k, k+1 lie inside both
 bool check_call(const Ex4dAttrParams *a, int32_t interp)
 {
     if (!a || a->Ns < 0 || a->Nd < 0) { snprintf(g_attr_err, sizeof(g_attr_err), "bad parameters"); return false; }
-    if (interp != EX4D_INTERP_CUBE && interp != EX4D_INTERP_LINEAR && interp != EX4D_INTERP_PCHIP) {
-        snprintf(g_attr_err, sizeof(g_attr_err), "unknown interpolator %d (0 cube, 1 linear, 2 pchip)", (int)interp); return false;
-    }
-    if (a->Nd > 0) {
-        const int before = interp == EX4D_INTERP_LINEAR ? 0 : 1, after = interp == EX4D_INTERP_LINEAR ? 1 : 2;
-        if (a->k < before || (int64_t)a->k + after >= (int64_t)a->K) {
-            snprintf(g_attr_err, sizeof(g_attr_err), "keyframe index %d needs k-%d..k+%d inside [0,%d)", a->k, before, after, a->K); return false;
-        }
-    }
-    return true;
+    if (!ex4d_known_interp(interp)) { snprintf(g_attr_err, sizeof(g_attr_err), EX4D_UNKNOWN_INTERP_FMT, (int)interp); return false; }
+    return ex4d_check_key_window(a, interp, -1, g_attr_err, sizeof(g_attr_err));
 }
 
 }  // namespace
@@ -344,9 +286,7 @@ int ex4d_attr_time_scalars(int32_t interp, double duration, double interval, dou
 {
     g_attr_err[0] = 0;
     if (!out) { snprintf(g_attr_err, sizeof(g_attr_err), "no output"); return EX4D_ERR_ARG; }
-    if (interp != EX4D_INTERP_CUBE && interp != EX4D_INTERP_LINEAR && interp != EX4D_INTERP_PCHIP) {
-        snprintf(g_attr_err, sizeof(g_attr_err), "unknown interpolator %d (0 cube, 1 linear, 2 pchip)", (int)interp); return EX4D_ERR_ARG;
-    }
+    if (!ex4d_known_interp(interp)) { snprintf(g_attr_err, sizeof(g_attr_err), EX4D_UNKNOWN_INTERP_FMT, (int)interp); return EX4D_ERR_ARG; }
     Ex4dAttrParams &a = *out;
     const double tp = timestamp + time_shift;
     // CPython float_divmod: mod = fmod(vx, wx); div = (vx - mod) / wx; adjust when the signs differ; floordiv = floor(div) rounded
@@ -390,9 +330,7 @@ int ex4d_attributes_forward_ex(const Ex4dAttrParams *a, int32_t interp,
     if (N == 0) return EX4D_OK;
 #define EX4D_LAUNCH_FWD(I) hipLaunchKernelGGL(attributes_fwd_kernel<I>, dim3((N + 255) / 256), dim3(256), 0, stream, *a, xyz, xyz_disp, rotation, \
         opacity, scaling, xyz_motion, rotation_motion, opacity_motion, dur_center, dur_var, scaling_motion, means3D, rotations, opacities, scales)
-    if (interp == EX4D_INTERP_LINEAR) EX4D_LAUNCH_FWD(EX4D_INTERP_LINEAR);
-    else if (interp == EX4D_INTERP_PCHIP) EX4D_LAUNCH_FWD(EX4D_INTERP_PCHIP);
-    else EX4D_LAUNCH_FWD(EX4D_INTERP_CUBE);
+    EX4D_DISPATCH_INTERP(interp, EX4D_LAUNCH_FWD);
 #undef EX4D_LAUNCH_FWD
     if (shs) {       // NULL: the caller feeds the rasterizer the four feature tensors directly (Ex4dSplitSH), nothing to gather
         const size_t total = (size_t)N * 12;
@@ -433,9 +371,7 @@ static int attributes_backward_impl(const Ex4dAttrParams *a, int32_t interp, int
         rotation_motion, opacity_motion, dur_center, dur_var, scaling_motion, g_means3D, g_rotations, g_opacities, g_scales, \
         g_xyz, g_xyz_disp, g_rotation, g_opacity, g_scaling, g_xyz_motion, g_rotation_motion, g_opacity_motion, g_dur_center, g_dur_var, \
         g_scaling_motion, sliced)
-    if (interp == EX4D_INTERP_LINEAR) EX4D_LAUNCH_BWD(EX4D_INTERP_LINEAR);
-    else if (interp == EX4D_INTERP_PCHIP) EX4D_LAUNCH_BWD(EX4D_INTERP_PCHIP);
-    else EX4D_LAUNCH_BWD(EX4D_INTERP_CUBE);
+    EX4D_DISPATCH_INTERP(interp, EX4D_LAUNCH_BWD);
 #undef EX4D_LAUNCH_BWD
     if (g_shs) {     // NULL: dL/dsh was written into the four gradient tensors by the rasterizer itself (Ex4dSplitSHGrad)
         const size_t total = (size_t)N * 12;
@@ -470,8 +406,8 @@ int ex4d_attributes_backward_sliced_ex(const Ex4dAttrParams *a, int32_t interp, 
     float *g_scaling_motion, float *g_features_dc_motion, float *g_features_rest_motion, int32_t *slices, void *stream_)
 {
     if (a && slices) {
-        const bool linear = interp == EX4D_INTERP_LINEAR;
-        slices[0] = linear ? a->k : a->k - 1; slices[1] = linear ? 2 : 4; slices[2] = a->k; slices[3] = 2;
+        const Ex4dKeyWindow w = ex4d_key_window(interp, a->k);
+        slices[0] = w.first; slices[1] = w.count; slices[2] = a->k; slices[3] = 2;
     }
     return attributes_backward_impl(a, interp, 1, xyz_motion, opacity, scaling, rotation_motion, opacity_motion, dur_center, dur_var, scaling_motion,
         g_means3D, g_rotations, g_opacities, g_scales, g_shs, g_xyz, g_xyz_disp, g_rotation, g_opacity, g_scaling, g_features_dc, g_features_rest,

@@ -11,6 +11,7 @@
 // (CR/auxiliary.h:43, :284; CR/forward.cu:112-116) are kept.  One thread per Gaussian, 256-thread
 // blocks (4 wave64); the kernels are HBM-bound (SH read / SH-grad write of 192 B per Gaussian).
 #include "ex4d_internal.h"
+#include "ex4d_camera.h"
 #include <atomic>
 #include <cstdlib>
 #include <cstdlib>
@@ -65,29 +66,15 @@ __device__ __forceinline__ int to_int_sat(float f)
     return (int)f;
 }
 
-__device__ __forceinline__ float3 xform4x3(float3 p, const float *m)
-{
-    return make_float3(m[0] * p.x + m[4] * p.y + m[8] * p.z + m[12],
-                       m[1] * p.x + m[5] * p.y + m[9] * p.z + m[13],
-                       m[2] * p.x + m[6] * p.y + m[10] * p.z + m[14]);
-}
-__device__ __forceinline__ float4 xform4x4(float3 p, const float *m)
-{
-    return make_float4(m[0] * p.x + m[4] * p.y + m[8] * p.z + m[12],
-                       m[1] * p.x + m[5] * p.y + m[9] * p.z + m[13],
-                       m[2] * p.x + m[6] * p.y + m[10] * p.z + m[14],
-                       m[3] * p.x + m[7] * p.y + m[11] * p.z + m[15]);
-}
-
-// frustum test of CR/auxiliary.h:267-294; returns visibility, p_view and the NDC xy
+// frustum test of CR/auxiliary.h:267-294; returns visibility, p_view and the NDC xy (the projection itself: ex4d_camera.h)
 __device__ __forceinline__ bool frustum_test(float3 p, const float *vm, const float *pm, float min_depth, float max_depth,
                                              float3 &p_view, float &ndc_x, float &ndc_y)
 {
-    float4 h = xform4x4(p, pm);
-    float inv_w = 1.0f / (h.w + 0.0000001f);
-    ndc_x = h.x * inv_w;
-    ndc_y = h.y * inv_w;
-    p_view = xform4x3(p, vm);
+    ProjectedPoint q;
+    project_point(p, vm, pm, q);
+    ndc_x = q.ndc_x;
+    ndc_y = q.ndc_y;
+    p_view = q.p_view;
     return !((p_view.z <= min_depth) || (p_view.z > max_depth) ||
              ((double)ndc_x < -1.3 || (double)ndc_x > 1.3 || (double)ndc_y < -1.3 || (double)ndc_y > 1.3));
 }
@@ -555,8 +542,8 @@ __global__ __launch_bounds__(256) void preprocess_fwd_kernel(
         const float lambda1 = mid + sqrtf(fmaxf(0.1f, mid * mid - det));
         const float lambda2 = mid - sqrtf(fmaxf(0.1f, mid * mid - det));
         const float my_radius = ceilf(3.f * sqrtf(fmaxf(lambda1, lambda2)));
-        pix_x = (float)((((double)ndc_x + 1.0) * (double)W - 1.0) * 0.5);   // ndc2Pix, CR/auxiliary.h:41-44
-        pix_y = (float)((((double)ndc_y + 1.0) * (double)H - 1.0) * 0.5);
+        pix_x = ndc_to_pix(ndc_x, W);
+        pix_y = ndc_to_pix(ndc_y, H);
         const int gx = (W + EX4D_TILE - 1) / EX4D_TILE, gy = (H + EX4D_TILE - 1) / EX4D_TILE;
         const int ri = to_int_sat(my_radius);
         int x0, y0, x1, y1;

@@ -15,6 +15,7 @@
 #include "../../include/ex4d_rasterizer.h"
 #include "../../include/ex4d_regularizers.h"
 #include "../../include/ex4d_trainer.h"
+#include "ex4d_keyframes.h"
 
 namespace {
 
@@ -157,7 +158,7 @@ Ex4dTrainer *ex4d_trainer_create(const Ex4dTrainerConfig *cfg, float *const *par
     for (int i = 0; i < EX4D_TRAINER_PARAMS && ok; i++) {
         t->param[i] = params[i];
         t->numel[i] = n[i];
-        t->grad_numel[i] = i == XYZ_MOTION ? Nd * 4 * 3 : (i == ROTATION_MOTION ? Nd * 2 * 4 : n[i]);
+        t->grad_numel[i] = i == XYZ_MOTION ? Nd * ex4d_key_window(t->interp, 0).count * 3 : (i == ROTATION_MOTION ? Nd * 2 * 4 : n[i]);
         if (n[i] > 0 && !params[i]) { tfail(1, "parameter %d is NULL but has %lld elements", i, (long long)n[i]); ok = false; break; }
         ok = ok && t->take(t->grad[i], (size_t)t->grad_numel[i]);
         if (cfg->optimizer) ok = ok && t->take(t->m[i], (size_t)n[i], true) && t->take(t->v[i], (size_t)n[i], true);
@@ -413,12 +414,11 @@ int ex4d_trainer_set_interp(Ex4dTrainer *t, int32_t interp)
 {
     t_err[0] = 0;
     if (!t) return tfail(EX4D_ERR_ARG, "null argument");
-    if (interp != EX4D_INTERP_CUBE && interp != EX4D_INTERP_LINEAR && interp != EX4D_INTERP_PCHIP)
-        return tfail(EX4D_ERR_ARG, "unknown interpolator %d (0 cube, 1 linear, 2 pchip)", (int)interp);
+    if (!ex4d_known_interp(interp)) return tfail(EX4D_ERR_ARG, EX4D_UNKNOWN_INTERP_FMT, (int)interp);
     if (t->frames > 0) return tfail(EX4D_ERR_ARG, "the interpolator is fixed once a step has run: set it right after ex4d_trainer_create");
     t->interp = interp;
-    // the position window of the sliced keyframe gradient: 2 slices for linear, 4 otherwise (the buffer was taken for 4)
-    t->grad_numel[XYZ_MOTION] = (int64_t)t->cfg.Nd * (interp == EX4D_INTERP_LINEAR ? 2 : 4) * 3;
+    // the position window of the sliced keyframe gradient (the buffer was taken for the cube's, the widest)
+    t->grad_numel[XYZ_MOTION] = (int64_t)t->cfg.Nd * ex4d_key_window(interp, 0).count * 3;
     return EX4D_OK;
 }
 

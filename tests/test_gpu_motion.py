@@ -7,6 +7,7 @@ scenes' row classes on the CPU oracle).
                    frames: at least half of all rows); rows at or behind `near` at either timestamp exact zeros; the remaining rows against
                    the float64 projection of the same float32 means within twice the error the rasterizer's own records have against it
   both             output buffers prefilled with 0xFF bytes; a captured graph replayed after the keyframes changed in place
+  backward, world  bit for bit two sliced attribute backwards (t0 fed -g, t1 fed g): windows, hints, g_xyz_disp; g_xyz exact zeros
   backward         1e-5 * max(1, |reference|inf) per tensor against the float64 restatement and against the reference's autograd (fixture),
                    NaN where the reference has NaN (pchip, constant tracks); dense gradient from the two windows; the hint; exact zeros
                    for g_xyz in world space and for rows under the depth rule; the two windows in ex4d_radam_step_sliced
@@ -232,6 +233,30 @@ def test_backward_matches_the_references_autograd_and_its_nan_pattern(hip_lib, i
             assert np.array_equal(np.isnan(got["_xyz_motion"].cpu().numpy()), z[f"{base}/nan32"])
             nans += int(z[f"{base}/nan32"].sum())
     assert (nans > 0) == (interp == "pchip")
+
+
+@pytest.mark.parametrize("Ns,Nd", mr.SHAPES)
+@pytest.mark.parametrize("interp", mr.INTERPS)
+def test_world_backward_is_two_sliced_attribute_backwards_bit_for_bit(hip_lib, interp, Ns, Nd):
+    """The adjoint's twin of the forward's pin: in world space the window of t1 carries the bits of the `_xyz_motion` slices the attribute
+    backward gives at t1 for g_means3D = g, the window of t0 those at t0 for -g (NaN patterns included: pchip, constant tracks); the static
+    rows get g_xyz = exact zeros and g_xyz_disp = the float32 sum of the two attribute results; the window hints are the attribute call's."""
+    from ex4dgs_amd.attributes import backward_raw
+    from ex4dgs_amd.motion import displacement_backward_raw
+    g = torch.randn(Ns + Nd, 3, generator=torch.Generator().manual_seed(11)).to(DEV)
+    for K, name, (t0, t1) in _cases(interp):
+        params = _params(mr.state(Ns, Nd, K))
+        s0, s1 = _scal(interp, t0, Ns, Nd, K), _scal(interp, t1, Ns, Nd, K)
+        g_xyz, g_disp, w0, w1, hint = displacement_backward_raw(s0, s1, *_xyz3(params), g, interp_type=interp)
+        (a0, hint0), (a1, hint1) = (backward_raw(s, params, [gm, None, None, None, None], with_shs=False, sliced=True, interp_type=interp)
+                                    for s, gm in ((s0, -g), (s1, g)))
+        assert hint == hint0[:2] + hint1[:2], (K, name)
+        assert w0.shape == a0[7].shape and torch.equal(_bits(w0), _bits(a0[7])), (K, name, "window of t0")
+        assert w1.shape == a1[7].shape and torch.equal(_bits(w1), _bits(a1[7])), (K, name, "window of t1")
+        assert g_xyz.shape == (Ns, 3) and not _bits(g_xyz).any(), (K, name, "g_xyz: exact (positive) zeros")
+        assert torch.equal(_bits(g_disp), _bits(a0[1] + a1[1])), (K, name, "g_xyz_disp")
+        if Nd and interp != "pchip":
+            assert torch.isfinite(w1).all() and w1.abs().max() > 0
 
 
 @pytest.mark.parametrize("interp,pair", [("cube", "adjacent"), ("cube", "far"), ("cube", "same"), ("linear", "adjacent"), ("linear", "reverse")])

@@ -238,7 +238,7 @@ def main():
     src = src.replace(a, a.replace("(256)", "(256, 4)")).replace('#include "ex4d_internal.h"', f'#include "{CSRC}/ex4d_internal.h"')
     hip = os.path.join(tmp, "pre.hip")
     open(hip, "w").write(src)
-    flags = build.COMMON + build.SOURCES["ex4d_preprocess.hip"] + [f"-I{ROOT}/include"]
+    flags = build.COMMON + build.SOURCES["ex4d_preprocess.hip"] + [f"-I{ROOT}/include", f"-I{CSRC}"]      # the copy lives outside csrc/: ex4d_camera.h
     run([build._hipcc()] + flags + ["-S", "--cuda-device-only", "-o", os.path.join(tmp, "dev.s"), hip])
     lines = open(os.path.join(tmp, "dev.s")).read().split("\n")
     others = [os.path.join(CSRC, f.replace(".hip", ".o")) for f in build.SOURCES if f != "ex4d_preprocess.hip"]

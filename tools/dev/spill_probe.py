@@ -29,7 +29,8 @@ def build_variant(dst, patch, info=None):
     tmp = os.path.join(dst, "ex4d_preprocess.hip")
     open(tmp, "w").write(src2.replace('#include "ex4d_internal.h"', f'#include "{CSRC}/ex4d_internal.h"'))
     obj = os.path.join(dst, "ex4d_preprocess.o")
-    cmd = [build._hipcc()] + build.COMMON + build.SOURCES["ex4d_preprocess.hip"] + ["-Rpass-analysis=kernel-resource-usage", "-c", tmp, "-o", obj]
+    # -I: the copy lives outside csrc/ and includes more of its headers than the one rewritten above (ex4d_camera.h)
+    cmd = [build._hipcc()] + build.COMMON + build.SOURCES["ex4d_preprocess.hip"] + [f"-I{CSRC}", "-Rpass-analysis=kernel-resource-usage", "-c", tmp, "-o", obj]
     r = subprocess.run(cmd, stderr=subprocess.PIPE, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     for m in re.finditer(r"Function Name: (\S+).*?VGPRs: (\d+).*?VGPRs Spill: (\d+)", r.stderr, re.S):
