@@ -192,6 +192,9 @@ PROTOTYPES = {
         _value("ex4d_flow_loss_scratch_floats", size, i32, i32),
         _status("ex4d_flow_loss_forward", i32, i32, vp, vp, i32, f32, vp, i32, f32, *[vp] * 4),
         _status("ex4d_flow_loss_backward", i32, i32, vp, vp, i32, f32, vp, i32, f32, *[vp] * 4),
+        _value("ex4d_depth_loss_scratch_bytes", size, i32, i32),
+        _status("ex4d_depth_loss_forward", i32, i32, vp, vp, i32, f32, vp, i32, f32, f32, i32, f32, *[vp] * 4),
+        _status("ex4d_depth_loss_backward", i32, i32, vp, vp, i32, f32, vp, i32, i32, f32, *[vp] * 4),
         _value("ex4d_frame_skssim_scratch_floats", size, i32, i32),
         _status("ex4d_frame_skssim", i32, i32, vp, vp, i32, *[vp] * 3),
         _status("ex4d_frame_skssim_u8", i32, i32, vp, vp, i32, vp, i32, *[vp] * 3))),

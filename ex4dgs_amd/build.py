@@ -30,6 +30,7 @@ SOURCES = {
     "ex4d_loss.hip": [],
     "ex4d_frames.hip": ["-ffp-contract=off"],       # PIL's resize (declared in ex4d_loss.h): the coefficient table's doubles must not fuse
     "ex4d_flow.hip": ["-ffp-contract=off"],         # flow loss on 16-bit ground truth (declared in ex4d_loss.h): the decode gives the reference's bits
+    "ex4d_depth.hip": ["-ffp-contract=off"],        # inverse-depth loss with a per-frame fit (declared in ex4d_loss.h): s g + o is a multiply then an add, in both passes
     "ex4d_optim.hip": ["-ffp-contract=off"],
     "ex4d_knn.hip": ["-ffp-contract=off"],
     "ex4d_densify.hip": ["-ffp-contract=off"],      # density control: threshold decisions and copied values follow torch's float32 ops

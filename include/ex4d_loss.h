@@ -156,6 +156,66 @@ int ex4d_flow_loss_backward(int32_t H, int32_t W, const float *flow, const void 
                             const float *acc, int32_t kind, float eps, const double *row /* device [4] */,
                             const float *grad_loss /* device [1] */, float *grad_flow, void *stream);
 
+/* DEPTH: supervising the rendered depth (the rasterizer's `depth` output, the alpha-normalised mean depth of CR/forward.cu:426-435) with
+ * the ground truth the reference's data layer carries (scene/dataset_readers.py:45 depth_path; utils/general_utils.py:32-36 load_depth):
+ * a 16-bit INVERSE-depth map, decoded on load.  Monocular inverse depth is known up to a scale and a shift, so the loss can fit both per
+ * frame, on the device.
+ *   depth DEVICE float32 [H,W].
+ *   gt    DEVICE [H,W]: gt_type EX4D_DEPTH_GT_U16 = uint16 codes at any 2-byte alignment (hence void *), EX4D_DEPTH_GT_F32 = float32
+ *         values (what load_depth returns after its host resize).  Raw value v = (float)code or the float itself; the ground truth is
+ *         VALID where v is finite and v > 0 (code 0: no measurement).
+ *   acc   DEVICE float32 [H,W] (the rasterizer's accumulated alpha) or NULL.  With acc: w = acc[p], and a pixel counts only where
+ *         acc > 0 (a pixel nothing was composited into carries max_depth, not a depth).  Without: w = 1.  A constant with no gradient.
+ * Per pixel, float32 (this file's kernels are compiled with -ffp-contract=off):
+ *     g = v * code_scale            one rounding: code_scale 1 gives load_depth's values, 2^-16 the usual normalised inverse depth;
+ *                                   equal values give equal bits in both ground-truth types
+ *     m = valid and (acc == NULL or acc > 0)
+ *     x = 1.0f / depth              IEEE division: the rendered inverse depth
+ *     gh = s * g + o                a multiply, then an add
+ *     r = x - gh;   rho = |r|  (EX4D_DEPTH_L1)   or   sqrt(r^2 + eps^2)  (EX4D_DEPTH_CHARBONNIER; eps finite and > 0)
+ *     loss = sum m w rho / max(n, 1),   n = sum m
+ * Pixels outside m are selected out: nothing behind them, a NaN included, reaches a sum or a gradient.  A non-finite or non-positive
+ * depth INSIDE m propagates and is counted in row[5].
+ * Alignment:
+ *   EX4D_DEPTH_ALIGN_GIVEN  s = scale, o = offset: the per-image constants a COLMAP-scaled pipeline supplies.
+ *   EX4D_DEPTH_ALIGN_FIT    the unweighted least-squares fit of gh to x over m, from five float64 sums n, Sg, Sx, Sgg, Sgx (products
+ *                           formed in double, where a product of two floats is exact), added in a fixed order: per lane, per workgroup,
+ *                           then across workgroups by one finishing wave.  det = n Sgg - Sg^2.  If n >= 2 and det > 1e-10 n Sgg:
+ *                           s = (n Sgx - Sg Sx) / det, o = (Sx - s Sg) / n; otherwise s = 0, o = Sx / max(n, 1).  The relative
+ *                           threshold makes a constant ground truth degenerate whatever the last bits of the sums are: a design
+ *                           constant, not a measurement.  s and o are rounded to float32 once; those floats are what the loss pass
+ *                           and the backward use.  scale and offset are ignored.
+ * Forward: loss DEVICE float[1]; row DEVICE double[6], all six written on every call:
+ *     row[0] the loss   row[1] n (exact)   row[2] s as used   row[3] o as used   row[4] sqrt(sum m r^2 / n), unweighted, 0 when n = 0
+ *     row[5] number of m pixels whose depth is not finite or <= 0 (exact)
+ * loss[0] is row[0] rounded once.  Every sum is double from the lane on.  scratch: ex4d_depth_loss_scratch_bytes(H, W) bytes (0 for a
+ * refused size), 8-byte aligned.
+ * Backward: grad_depth DEVICE [H,W], fully written: grad_loss[0] * m w / max(n, 1) * rho'(r) * (-x x), rho'(r) = sign(r) with
+ * sign(0) = 0 for L1 and r / rho for Charbonnier.  THE FIT IS DETACHED: s, o and n are read from row, the forward's row of the same
+ * inputs, as constants.  Exact zeros outside m, and everywhere when n = 0.  grad_loss DEVICE float[1].
+ * Refused before any launch, with a message: H or W <= 0, an unknown kind, align or gt_type, Charbonnier with eps <= 0 or not finite,
+ * code_scale not finite or <= 0, GIVEN with a non-finite scale or offset, a NULL required pointer, a scratch that is not 8-byte aligned.
+ * No allocation, no copy, no synchronisation, no atomics: the calls can be captured into a graph.  Equal inputs give equal bits.
+ * Launches: FIT forward four (moments, solve, loss, finish), GIVEN forward two (loss, finish), backward one.
+ * Tiling: a lane owns EX4D_DEPTH_PIXELS_PER_LANE consecutive pixels of the flat [H W] index, a workgroup has EX4D_DEPTH_THREADS lanes, and
+ * the one wave that adds the workgroups' partial sums takes EX4D_DEPTH_FOLD of them per step. */
+#define EX4D_DEPTH_L1 0
+#define EX4D_DEPTH_CHARBONNIER 1
+#define EX4D_DEPTH_ALIGN_GIVEN 0
+#define EX4D_DEPTH_ALIGN_FIT 1
+#define EX4D_DEPTH_GT_U16 0
+#define EX4D_DEPTH_GT_F32 1
+#define EX4D_DEPTH_PIXELS_PER_LANE 4
+#define EX4D_DEPTH_THREADS 256
+#define EX4D_DEPTH_FOLD 64
+size_t ex4d_depth_loss_scratch_bytes(int32_t H, int32_t W);
+int ex4d_depth_loss_forward(int32_t H, int32_t W, const float *depth, const void *gt, int32_t gt_type, float code_scale,
+                            const float *acc, int32_t align, float scale, float offset, int32_t kind, float eps, float *loss,
+                            double *row /* device [6] */, void *scratch, void *stream);
+int ex4d_depth_loss_backward(int32_t H, int32_t W, const float *depth, const void *gt, int32_t gt_type, float code_scale,
+                             const float *acc, int32_t align, int32_t kind, float eps, const double *row /* device [6] */,
+                             const float *grad_loss /* device [1] */, float *grad_depth, void *stream);
+
 /* scikit-image's SSIM of a rendered view: the SKSSIM and SKSSIM2 entries of render.py:78-79,
  *     sk_ssim(render, gt, data_range=R, multichannel=True, channel_axis=0)   with R = 1 and R = 2,
  * as scikit-image 0.22 and later read that call (multichannel is ignored, channel_axis=0 holds; earlier releases fail on a [3,H,W]
