@@ -126,7 +126,7 @@ def build(force=False, verbose=False, extra_flags=()):
                os.path.join(HERE, "..", "include", "ex4d_attributes.h"), os.path.join(HERE, "..", "include", "ex4d_loss.h"), os.path.join(HERE, "..", "include", "ex4d_optim.h"), os.path.join(HERE, "..", "include", "ex4d_knn.h"), os.path.join(HERE, "..", "include", "ex4d_trainer.h"),
                os.path.join(HERE, "..", "include", "ex4d_densify.h"), os.path.join(HERE, "..", "include", "ex4d_regularizers.h"),
                os.path.join(CSRC, "ex4d_reg_rows.h"), os.path.join(CSRC, "ex4d_keyframes.h"), os.path.join(CSRC, "ex4d_camera.h"),
-               os.path.abspath(__file__)]
+               os.path.join(CSRC, "ex4d_pixel_stream.h"), os.path.join(CSRC, "ex4d_host_error.h"), os.path.abspath(__file__)]
     objs = []
     for src, flags in SOURCES.items():
         s = os.path.join(CSRC, src)

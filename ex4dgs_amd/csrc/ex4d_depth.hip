@@ -9,113 +9,59 @@
 // with (s, o) given, or the least-squares fit of gh to x over m.  This file is compiled with -ffp-contract=off: the multiply and the add
 // of gh round separately, and the forward and the backward see the same residual.
 //
-// A STREAMING PASS over flat pixels p = y W + x, tiled as the flow loss is (ex4d_flow.hip): a lane owns EX4D_DEPTH_PIXELS_PER_LANE = 4
-// consecutive pixels, a workgroup of 256 lanes 1024.  A float plane is read (written) as one 16-byte vector per lane where the lane's
-// first element is 16-byte aligned, the four uint16 codes as one 8-byte vector where their address is 8-byte aligned; anything else, and
-// the last, partial lane of a frame, goes element by element.  Pixels outside m are SELECTED out, never multiplied by zero.
-// Every sum is double from the lane on (a product of two floats is exact there): wave shuffle, LDS, the four waves in a fixed order,
-// one row of partials per workgroup in scratch; ONE WAVE then adds the workgroups' rows, lane i taking workgroups i, i + 64, ... in
-// order, then the shuffle tree.  FIT forward: moments -> solve (that wave; writes float s, o to the head of scratch) -> loss -> finish
-// (that wave again; writes loss and row).  GIVEN forward: loss -> finish.  Backward: one launch; s, o and n are read from the forward's
-// row on the device, so the fit is a constant there.  No atomics, no allocation, no synchronisation.
+// THE PASS is the streaming pass of ex4d_pixel_stream.h: four consecutive pixels per lane, float planes through load4 / store4, a row of
+// sums per workgroup, one wave folding the rows in a fixed order.  What is the depth loss's own: the four uint16 codes of a lane go as
+// one 8-byte vector where their address is 8-byte aligned, element by element otherwise and in the last, partial lane.  Pixels outside m
+// are SELECTED out, never multiplied by zero.  Every sum is double from the lane on (a product of two floats is exact there).
+// FIT forward: moments -> solve (the folding wave; writes float s, o to the head of scratch) -> loss -> finish (that wave again; writes
+// loss and row).  GIVEN forward: loss -> finish.  Backward: one launch; s, o and n are read from the forward's row on the device, so
+// the fit is a constant there.  No atomics, no allocation, no synchronisation.
 #include "ex4d_internal.h"
-#include "../../include/ex4d_loss.h"
-#include <cmath>
-#include <cstdio>
-
-char *ex4d_loss_error_buffer(size_t *capacity);         // ex4d_loss.hip: the text ex4d_loss_last_error returns
+#include "ex4d_pixel_stream.h"
+#define EX4D_ERROR_BUFFER ex4d_loss_error_buffer        // ex4d_loss.hip: the text ex4d_loss_last_error returns
+#include "ex4d_host_error.h"
 
 namespace {
 
-#define DP_PPL EX4D_DEPTH_PIXELS_PER_LANE
-#define DP_THREADS EX4D_DEPTH_THREADS
-#define DP_WG_PIXELS (DP_PPL * DP_THREADS)
-#define DP_FOLD EX4D_DEPTH_FOLD
 #define DP_MOMENTS 5                   // n, Sg, Sx, Sgg, Sgx
 #define DP_SUMS 4                      // weighted rho, n, r^2, m pixels with a bad depth
 #define DP_HEAD_BYTES 16               // scratch: float s, o (the fit), then the moments' rows, then the loss pass's rows
-static_assert(DP_PPL == 4, "a lane's pixels are one float4 per plane and one 8-byte vector of codes");
-static_assert(DP_THREADS == 256 && DP_FOLD == 64, "four waves per workgroup; the solve and finish kernels are one wave");
-
-int fail(const char *text)
-{
-    size_t cap = 0;
-    char *buf = ex4d_loss_error_buffer(&cap);
-    snprintf(buf, cap, "%s", text);
-    return EX4D_ERR_ARG;
-}
-
-int launch_status(const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return EX4D_OK;
-    size_t cap = 0;
-    char *buf = ex4d_loss_error_buffer(&cap);
-    snprintf(buf, cap, "%s: launch failed: %s", what, hipGetErrorString(e));
-    return EX4D_ERR_HIP;
-}
-
-// ---- a lane's n <= 4 consecutive elements of a float plane, from element p0 (a multiple of 4)
-__device__ __forceinline__ void load4(const float *__restrict__ plane, long long p0, int n, float (&o)[DP_PPL], float fill)
-{
-    const float *q = plane + p0;
-    if (n == DP_PPL && ((uintptr_t)q & 15) == 0) {
-        const float4 t = *reinterpret_cast<const float4 *>(q);
-        o[0] = t.x; o[1] = t.y; o[2] = t.z; o[3] = t.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < DP_PPL; j++) o[j] = j < n ? q[j] : fill;
-    }
-}
-
-__device__ __forceinline__ void store4(float *__restrict__ plane, long long p0, int n, const float (&v)[DP_PPL])
-{
-    float *q = plane + p0;
-    if (n == DP_PPL && ((uintptr_t)q & 15) == 0) {
-        *reinterpret_cast<float4 *>(q) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-#pragma unroll
-        for (int j = 0; j < DP_PPL; j++)
-            if (j < n) q[j] = v[j];
-    }
-}
 
 // ---- the raw ground-truth values of the lane's pixels; pixels j >= n come back 0 (no measurement)
 template <int GT>
-__device__ __forceinline__ void load_raw(const void *__restrict__ gt, long long p0, int n, float (&v)[DP_PPL])
+__device__ __forceinline__ void load_raw(const void *__restrict__ gt, long long p0, int n, float (&v)[PS_PPL])
 {
     if (GT == EX4D_DEPTH_GT_F32) {
         load4(static_cast<const float *>(gt), p0, n, v, 0.f);
     } else {
         const uint16_t *q = static_cast<const uint16_t *>(gt) + p0;
-        if (n == DP_PPL && ((uintptr_t)q & 7) == 0) {
+        if (n == PS_PPL && ((uintptr_t)q & 7) == 0) {
             const uint2 t = *reinterpret_cast<const uint2 *>(q);
             v[0] = (float)(t.x & 0xffffu); v[1] = (float)(t.x >> 16);
             v[2] = (float)(t.y & 0xffffu); v[3] = (float)(t.y >> 16);
         } else {
 #pragma unroll
-            for (int j = 0; j < DP_PPL; j++) v[j] = j < n ? (float)q[j] : 0.f;
+            for (int j = 0; j < PS_PPL; j++) v[j] = j < n ? (float)q[j] : 0.f;
         }
     }
 }
 
-__device__ __forceinline__ bool finite(float x) { return fabsf(x) <= 3.402823466e+38f; }
 __device__ __forceinline__ bool measured(float v) { return v > 0.f && finite(v); }
 
 // ---- a lane's pixels: depth, decoded ground truth, weight, mask
-struct Pixels { float d[DP_PPL], g[DP_PPL], w[DP_PPL]; bool m[DP_PPL]; };
+struct Pixels { float d[PS_PPL], g[PS_PPL], w[PS_PPL]; bool m[PS_PPL]; };
 
 template <int GT>
 __device__ __forceinline__ Pixels load_pixels(long long p0, int n, const float *__restrict__ depth, const void *__restrict__ gt,
                                               float code_scale, const float *__restrict__ acc)
 {
     Pixels px;
-    float v[DP_PPL];
+    float v[PS_PPL];
     load4(depth, p0, n, px.d, 1.f);
     load_raw<GT>(gt, p0, n, v);
     if (acc) load4(acc, p0, n, px.w, 0.f);
 #pragma unroll
-    for (int j = 0; j < DP_PPL; j++) {
+    for (int j = 0; j < PS_PPL; j++) {
         px.g[j] = v[j] * code_scale;
         px.m[j] = measured(v[j]) && (!acc || px.w[j] > 0.f);
         if (!acc) px.w[j] = 1.f;
@@ -123,52 +69,8 @@ __device__ __forceinline__ Pixels load_pixels(long long p0, int n, const float *
     return px;
 }
 
-// ---- N double sums over the workgroup's 256 threads into one row of partials: wave shuffle, then LDS, the four waves in a fixed order
-template <int N>
-__device__ __forceinline__ void wave_sum(double (&v)[N])
-{
-#pragma unroll
-    for (int q = 0; q < N; q++) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v[q] += __shfl_xor(v[q], o, 64);
-    }
-}
-
-template <int N>
-__device__ __forceinline__ void workgroup_row(double (&sums)[N], double *__restrict__ rows)
-{
-    __shared__ double s[N][DP_THREADS / 64];
-    wave_sum(sums);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int q = 0; q < N; q++) s[q][wave] = sums[q];
-    }
-    __syncthreads();
-    if (threadIdx.x < N) {
-        const int q = threadIdx.x;
-        rows[N * (size_t)blockIdx.x + q] = s[q][0] + s[q][1] + s[q][2] + s[q][3];
-    }
-}
-
-// the one wave's sum of the workgroups' rows: lane i takes workgroups i, i + 64, ... in order, then the shuffle tree
-template <int N>
-__device__ __forceinline__ void fold_rows(int nblocks, const double *__restrict__ rows, double (&sum)[N])
-{
-#pragma unroll
-    for (int q = 0; q < N; q++) sum[q] = 0.0;
-    for (int i = threadIdx.x; i < nblocks; i += DP_FOLD) {
-#pragma unroll
-        for (int q = 0; q < N; q++) sum[q] += rows[N * (size_t)i + q];
-    }
-    wave_sum(sum);
-}
-
-__device__ __forceinline__ long long first_pixel() { return ((long long)blockIdx.x * DP_THREADS + threadIdx.x) * DP_PPL; }
-__device__ __forceinline__ int pixels_from(long long p0, long long HW) { return p0 >= HW ? 0 : (HW - p0 < DP_PPL ? (int)(HW - p0) : DP_PPL); }
-
 template <int GT>
-__global__ __launch_bounds__(DP_THREADS) void depth_moments_kernel(long long HW, const float *__restrict__ depth,
+__global__ __launch_bounds__(PS_THREADS) void depth_moments_kernel(long long HW, const float *__restrict__ depth,
     const void *__restrict__ gt, float code_scale, const float *__restrict__ acc, double *__restrict__ rows)
 {
     const long long p0 = first_pixel();
@@ -177,7 +79,7 @@ __global__ __launch_bounds__(DP_THREADS) void depth_moments_kernel(long long HW,
     if (n > 0) {
         const Pixels px = load_pixels<GT>(p0, n, depth, gt, code_scale, acc);
 #pragma unroll
-        for (int j = 0; j < DP_PPL; j++) {
+        for (int j = 0; j < PS_PPL; j++) {
             const double g = (double)px.g[j], x = (double)(1.0f / px.d[j]);
             sums[0] += px.m[j] ? 1.0 : 0.0;
             sums[1] += px.m[j] ? g : 0.0;
@@ -189,7 +91,7 @@ __global__ __launch_bounds__(DP_THREADS) void depth_moments_kernel(long long HW,
     workgroup_row(sums, rows);
 }
 
-__global__ __launch_bounds__(DP_FOLD) void depth_solve_kernel(int nblocks, const double *__restrict__ rows, float *__restrict__ fit)
+__global__ __launch_bounds__(PS_FOLD) void depth_solve_kernel(int nblocks, const double *__restrict__ rows, float *__restrict__ fit)
 {
     double sum[DP_MOMENTS];
     fold_rows(nblocks, rows, sum);
@@ -207,7 +109,7 @@ __global__ __launch_bounds__(DP_FOLD) void depth_solve_kernel(int nblocks, const
 }
 
 template <int GT>
-__global__ __launch_bounds__(DP_THREADS) void depth_loss_kernel(long long HW, const float *__restrict__ depth,
+__global__ __launch_bounds__(PS_THREADS) void depth_loss_kernel(long long HW, const float *__restrict__ depth,
     const void *__restrict__ gt, float code_scale, const float *__restrict__ acc, const float *__restrict__ fit, float scale, float offset,
     int kind, float eps, double *__restrict__ rows)
 {
@@ -219,7 +121,7 @@ __global__ __launch_bounds__(DP_THREADS) void depth_loss_kernel(long long HW, co
         const Pixels px = load_pixels<GT>(p0, n, depth, gt, code_scale, acc);
         const float eps2 = eps * eps;
 #pragma unroll
-        for (int j = 0; j < DP_PPL; j++) {
+        for (int j = 0; j < PS_PPL; j++) {
             const float d = px.d[j];
             const float r = 1.0f / d - (s * px.g[j] + o);
             const float rho = kind == EX4D_DEPTH_L1 ? fabsf(r) : sqrtf(r * r + eps2);
@@ -233,7 +135,7 @@ __global__ __launch_bounds__(DP_THREADS) void depth_loss_kernel(long long HW, co
     workgroup_row(sums, rows);
 }
 
-__global__ __launch_bounds__(DP_FOLD) void depth_finish_kernel(int nblocks, const double *__restrict__ rows, const float *__restrict__ fit,
+__global__ __launch_bounds__(PS_FOLD) void depth_finish_kernel(int nblocks, const double *__restrict__ rows, const float *__restrict__ fit,
     float scale, float offset, float *__restrict__ loss, double *__restrict__ row)
 {
     double sum[DP_SUMS];
@@ -252,7 +154,7 @@ __global__ __launch_bounds__(DP_FOLD) void depth_finish_kernel(int nblocks, cons
 }
 
 template <int GT>
-__global__ __launch_bounds__(DP_THREADS) void depth_loss_bwd_kernel(long long HW, const float *__restrict__ depth,
+__global__ __launch_bounds__(PS_THREADS) void depth_loss_bwd_kernel(long long HW, const float *__restrict__ depth,
     const void *__restrict__ gt, float code_scale, const float *__restrict__ acc, int kind, float eps, const double *__restrict__ row,
     const float *__restrict__ grad_loss, float *__restrict__ grad_depth)
 {
@@ -264,9 +166,9 @@ __global__ __launch_bounds__(DP_THREADS) void depth_loss_bwd_kernel(long long HW
     const float k = grad_loss[0] / (float)(count > 1.0 ? count : 1.0);
     const Pixels px = load_pixels<GT>(p0, n, depth, gt, code_scale, acc);
     const float eps2 = eps * eps;
-    float out[DP_PPL];
+    float out[PS_PPL];
 #pragma unroll
-    for (int j = 0; j < DP_PPL; j++) {
+    for (int j = 0; j < PS_PPL; j++) {
         const float x = 1.0f / px.d[j];
         const float r = x - (s * px.g[j] + o);
         const float dr = kind == EX4D_DEPTH_L1 ? (float)((r > 0.f) - (r < 0.f)) : r / sqrtf(r * r + eps2);
@@ -276,37 +178,23 @@ __global__ __launch_bounds__(DP_THREADS) void depth_loss_bwd_kernel(long long HW
     store4(grad_depth, p0, n, out);
 }
 
-inline long long blocks_of(long long HW) { return (HW + DP_WG_PIXELS - 1) / DP_WG_PIXELS; }
-
 // what both calls refuse before any launch; NULL where the arguments are fine
 const char *refusal(int H, int W, const void *depth, const void *gt, int gt_type, float code_scale, int align, int kind, float eps)
 {
-    static char text[160];
-    if (H <= 0 || W <= 0) { snprintf(text, sizeof(text), "depth loss: image %d x %d: H and W must be positive", H, W); return text; }
-    if (blocks_of((long long)H * W) > 0x7fffffffLL) { snprintf(text, sizeof(text), "depth loss: image %d x %d: too many pixels for one launch", H, W); return text; }
+    static char text[160], text_late[160];
+    const char *own = nullptr, *late = nullptr;
     if (gt_type != EX4D_DEPTH_GT_U16 && gt_type != EX4D_DEPTH_GT_F32) {
         snprintf(text, sizeof(text), "depth loss: gt_type %d: EX4D_DEPTH_GT_U16 (0) or EX4D_DEPTH_GT_F32 (1)", gt_type);
-        return text;
-    }
-    if (align != EX4D_DEPTH_ALIGN_GIVEN && align != EX4D_DEPTH_ALIGN_FIT) {
+        own = text;
+    } else if (align != EX4D_DEPTH_ALIGN_GIVEN && align != EX4D_DEPTH_ALIGN_FIT) {
         snprintf(text, sizeof(text), "depth loss: align %d: EX4D_DEPTH_ALIGN_GIVEN (0) or EX4D_DEPTH_ALIGN_FIT (1)", align);
-        return text;
-    }
-    if (kind != EX4D_DEPTH_L1 && kind != EX4D_DEPTH_CHARBONNIER) {
-        snprintf(text, sizeof(text), "depth loss: kind %d: EX4D_DEPTH_L1 (0) or EX4D_DEPTH_CHARBONNIER (1)", kind);
-        return text;
-    }
-    if (kind == EX4D_DEPTH_CHARBONNIER && !(eps > 0.f && std::isfinite(eps))) {
-        snprintf(text, sizeof(text), "depth loss: eps %g: Charbonnier needs a finite eps > 0", (double)eps);
-        return text;
+        own = text;
     }
     if (!(code_scale > 0.f && std::isfinite(code_scale))) {
-        snprintf(text, sizeof(text), "depth loss: code_scale %g: must be finite and > 0", (double)code_scale);
-        return text;
+        snprintf(text_late, sizeof(text_late), "depth loss: code_scale %g: must be finite and > 0", (double)code_scale);
+        late = text_late;
     }
-    if (!depth) return "depth loss: depth is NULL";
-    if (!gt) return "depth loss: gt is NULL";
-    return nullptr;
+    return pixel_loss_refusal("depth loss", "EX4D_DEPTH", H, W, own, kind, eps, late, "depth", depth, gt);
 }
 
 }  // namespace
@@ -323,18 +211,17 @@ int ex4d_depth_loss_forward(int32_t H, int32_t W, const float *depth, const void
                             const float *acc, int32_t align, float scale, float offset, int32_t kind, float eps, float *loss,
                             double *row, void *scratch, void *stream_)
 {
-    size_t cap = 0;
-    ex4d_loss_error_buffer(&cap)[0] = 0;
-    if (const char *why = refusal(H, W, depth, gt, gt_type, code_scale, align, kind, eps)) return fail(why);
+    clear_error();
+    if (const char *why = refusal(H, W, depth, gt, gt_type, code_scale, align, kind, eps)) return fail(EX4D_ERR_ARG, why);
     if (align == EX4D_DEPTH_ALIGN_GIVEN && !(std::isfinite(scale) && std::isfinite(offset))) {
         char text[160];
         snprintf(text, sizeof(text), "depth loss: scale %g, offset %g: EX4D_DEPTH_ALIGN_GIVEN needs both finite", (double)scale, (double)offset);
-        return fail(text);
+        return fail(EX4D_ERR_ARG, text);
     }
-    if (!loss) return fail("depth loss: loss is NULL");
-    if (!row) return fail("depth loss: row is NULL");
-    if (!scratch) return fail("depth loss: scratch is NULL");
-    if ((uintptr_t)scratch & 7) return fail("depth loss: scratch is not 8-byte aligned");
+    if (!loss) return fail(EX4D_ERR_ARG, "depth loss: loss is NULL");
+    if (!row) return fail(EX4D_ERR_ARG, "depth loss: row is NULL");
+    if (!scratch) return fail(EX4D_ERR_ARG, "depth loss: scratch is NULL");
+    if ((uintptr_t)scratch & 7) return fail(EX4D_ERR_ARG, "depth loss: scratch is not 8-byte aligned");
     const long long HW = (long long)H * W;
     const int nblocks = (int)blocks_of(HW);
     float *head = static_cast<float *>(scratch);
@@ -345,16 +232,16 @@ int ex4d_depth_loss_forward(int32_t H, int32_t W, const float *depth, const void
     hipStream_t stream = (hipStream_t)stream_;
     if (fit) {
         if (u16)
-            hipLaunchKernelGGL(depth_moments_kernel<EX4D_DEPTH_GT_U16>, dim3(nblocks), dim3(DP_THREADS), 0, stream, HW, depth, gt, code_scale, acc, moments);
+            hipLaunchKernelGGL(depth_moments_kernel<EX4D_DEPTH_GT_U16>, dim3(nblocks), dim3(PS_THREADS), 0, stream, HW, depth, gt, code_scale, acc, moments);
         else
-            hipLaunchKernelGGL(depth_moments_kernel<EX4D_DEPTH_GT_F32>, dim3(nblocks), dim3(DP_THREADS), 0, stream, HW, depth, gt, code_scale, acc, moments);
-        hipLaunchKernelGGL(depth_solve_kernel, dim3(1), dim3(DP_FOLD), 0, stream, nblocks, moments, head);
+            hipLaunchKernelGGL(depth_moments_kernel<EX4D_DEPTH_GT_F32>, dim3(nblocks), dim3(PS_THREADS), 0, stream, HW, depth, gt, code_scale, acc, moments);
+        hipLaunchKernelGGL(depth_solve_kernel, dim3(1), dim3(PS_FOLD), 0, stream, nblocks, moments, head);
     }
     if (u16)
-        hipLaunchKernelGGL(depth_loss_kernel<EX4D_DEPTH_GT_U16>, dim3(nblocks), dim3(DP_THREADS), 0, stream, HW, depth, gt, code_scale, acc, fit, scale, offset, kind, eps, sums);
+        hipLaunchKernelGGL(depth_loss_kernel<EX4D_DEPTH_GT_U16>, dim3(nblocks), dim3(PS_THREADS), 0, stream, HW, depth, gt, code_scale, acc, fit, scale, offset, kind, eps, sums);
     else
-        hipLaunchKernelGGL(depth_loss_kernel<EX4D_DEPTH_GT_F32>, dim3(nblocks), dim3(DP_THREADS), 0, stream, HW, depth, gt, code_scale, acc, fit, scale, offset, kind, eps, sums);
-    hipLaunchKernelGGL(depth_finish_kernel, dim3(1), dim3(DP_FOLD), 0, stream, nblocks, sums, fit, scale, offset, loss, row);
+        hipLaunchKernelGGL(depth_loss_kernel<EX4D_DEPTH_GT_F32>, dim3(nblocks), dim3(PS_THREADS), 0, stream, HW, depth, gt, code_scale, acc, fit, scale, offset, kind, eps, sums);
+    hipLaunchKernelGGL(depth_finish_kernel, dim3(1), dim3(PS_FOLD), 0, stream, nblocks, sums, fit, scale, offset, loss, row);
     return launch_status("ex4d_depth_loss_forward");
 }
 
@@ -362,19 +249,18 @@ int ex4d_depth_loss_backward(int32_t H, int32_t W, const float *depth, const voi
                              const float *acc, int32_t align, int32_t kind, float eps, const double *row, const float *grad_loss,
                              float *grad_depth, void *stream_)
 {
-    size_t cap = 0;
-    ex4d_loss_error_buffer(&cap)[0] = 0;
-    if (const char *why = refusal(H, W, depth, gt, gt_type, code_scale, align, kind, eps)) return fail(why);
-    if (!row) return fail("depth loss: row is NULL");
-    if (!grad_loss) return fail("depth loss: grad_loss is NULL");
-    if (!grad_depth) return fail("depth loss: grad_depth is NULL");
+    clear_error();
+    if (const char *why = refusal(H, W, depth, gt, gt_type, code_scale, align, kind, eps)) return fail(EX4D_ERR_ARG, why);
+    if (!row) return fail(EX4D_ERR_ARG, "depth loss: row is NULL");
+    if (!grad_loss) return fail(EX4D_ERR_ARG, "depth loss: grad_loss is NULL");
+    if (!grad_depth) return fail(EX4D_ERR_ARG, "depth loss: grad_depth is NULL");
     const long long HW = (long long)H * W;
     const int nblocks = (int)blocks_of(HW);
     hipStream_t stream = (hipStream_t)stream_;
     if (gt_type == EX4D_DEPTH_GT_U16)
-        hipLaunchKernelGGL(depth_loss_bwd_kernel<EX4D_DEPTH_GT_U16>, dim3(nblocks), dim3(DP_THREADS), 0, stream, HW, depth, gt, code_scale, acc, kind, eps, row, grad_loss, grad_depth);
+        hipLaunchKernelGGL(depth_loss_bwd_kernel<EX4D_DEPTH_GT_U16>, dim3(nblocks), dim3(PS_THREADS), 0, stream, HW, depth, gt, code_scale, acc, kind, eps, row, grad_loss, grad_depth);
     else
-        hipLaunchKernelGGL(depth_loss_bwd_kernel<EX4D_DEPTH_GT_F32>, dim3(nblocks), dim3(DP_THREADS), 0, stream, HW, depth, gt, code_scale, acc, kind, eps, row, grad_loss, grad_depth);
+        hipLaunchKernelGGL(depth_loss_bwd_kernel<EX4D_DEPTH_GT_F32>, dim3(nblocks), dim3(PS_THREADS), 0, stream, HW, depth, gt, code_scale, acc, kind, eps, row, grad_loss, grad_depth);
     return launch_status("ex4d_depth_loss_backward");
 }
 

@@ -16,11 +16,10 @@
 #include "ex4d_internal.h"
 #include "../../include/ex4d_loss.h"
 #include <cmath>
-#include <cstdio>
 #include <cstring>
 #include <vector>
-
-char *ex4d_loss_error_buffer(size_t *capacity);         // ex4d_loss.hip: the text ex4d_loss_last_error returns
+#define EX4D_ERROR_BUFFER ex4d_loss_error_buffer        // ex4d_loss.hip: the text ex4d_loss_last_error returns
+#include "ex4d_host_error.h"
 
 namespace {
 
@@ -29,30 +28,6 @@ namespace {
 static_assert(EX4D_RESIZE_H_PIXELS * EX4D_RESIZE_H_ROWS == RZ_THREADS, "horizontal pass: one lane per pixel of the workgroup's tile");
 static_assert(EX4D_RESIZE_V_BYTES / 4 * EX4D_RESIZE_V_ROWS == RZ_THREADS, "vertical pass: one lane per dword of the workgroup's tile");
 static_assert(EX4D_RESIZE_H_PIXELS == 64 && EX4D_RESIZE_V_BYTES / 4 == 64, "a wave is one row of a tile: the row's table entry is uniform in it");
-
-int fail(int status, const char *text)
-{
-    size_t cap = 0;
-    char *buf = ex4d_loss_error_buffer(&cap);
-    snprintf(buf, cap, "%s", text);
-    return status;
-}
-
-void clear_error()
-{
-    size_t cap = 0;
-    ex4d_loss_error_buffer(&cap)[0] = 0;
-}
-
-int launch_status(const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return EX4D_OK;
-    size_t cap = 0;
-    char *buf = ex4d_loss_error_buffer(&cap);
-    snprintf(buf, cap, "%s: launch failed: %s", what, hipGetErrorString(e));
-    return EX4D_ERR_HIP;
-}
 
 // ---- the table (host, double precision, PIL's precompute_coeffs and normalize_coeffs_8bpc)
 double filter_value(int filter, double x)

@@ -13,9 +13,8 @@
 // ffp-contract is off for this file: decisions and generated values follow torch's float32 op order.
 #include "ex4d_internal.h"
 #include "../../include/ex4d_densify.h"
-#include <cstdio>
-
-char *ex4d_densify_error_buffer(size_t *capacity);      // ex4d_densify.hip: the text ex4d_densify_last_error returns
+#define EX4D_ERROR_BUFFER ex4d_densify_error_buffer     // ex4d_densify.hip: the text ex4d_densify_last_error returns
+#include "ex4d_host_error.h"
 
 namespace {
 
@@ -27,30 +26,6 @@ namespace {
 
 // select scratch, in 32-bit words: four histograms, then the state
 enum { SS_HIST = 0, SS_COUNT = 4 * GR_BINS, SS_MAX, SS_PREFIX, SS_RANK, SS_BELOW, SS_LO_BITS, SS_NEED_NEXT, SS_NEXT_MIN, SS_WEIGHT, SS_WORDS };
-
-int fail(int status, const char *text)
-{
-    size_t cap = 0;
-    char *buf = ex4d_densify_error_buffer(&cap);
-    snprintf(buf, cap, "%s", text);
-    return status;
-}
-
-int launch_status(const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return EX4D_OK;
-    size_t cap = 0;
-    char *buf = ex4d_densify_error_buffer(&cap);
-    snprintf(buf, cap, "%s: launch failed: %s", what, hipGetErrorString(e));
-    return EX4D_ERR_HIP;
-}
-
-void clear_error()
-{
-    size_t cap = 0;
-    ex4d_densify_error_buffer(&cap)[0] = 0;
-}
 
 inline unsigned grid_for(long long n)
 {
@@ -512,10 +487,9 @@ int ex4d_growth_append(const Ex4dGrowthTensor *tensors, int32_t count, const Ex4
             (reads_stats && t.width != 2) ||
             (g.n_new > 0 && ((reads_stats && !g.stats) || ((t.rule == EX4D_GROW_COPY || t.rule == EX4D_GROW_XYZ || t.rule == EX4D_GROW_ROTATION) && !t.src0) ||
                              (t.rule == EX4D_GROW_XYZ && !t.src1)))) {
-            size_t cap = 0;
-            char *buf = ex4d_densify_error_buffer(&cap);
-            snprintf(buf, cap, "growth_append: tensor %d: bad shape, rule or null pointer", i);
-            return EX4D_ERR_ARG;
+            char text[96];
+            snprintf(text, sizeof(text), "growth_append: tensor %d: bad shape, rule or null pointer", i);
+            return fail(EX4D_ERR_ARG, text);
         }
         const long long numel = (stats ? (long long)EX4D_DENSIFY_STATS : (long long)t.width) * (t.old_rows + g.n_new);
         if (numel == 0) continue;

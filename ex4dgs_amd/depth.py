@@ -21,21 +21,13 @@ in the mask, s, o, RMSE of r, mask pixels whose depth is not finite or <= 0) for
 """
 import torch
 
-from . import _abi
+from . import _abi, _pixel_loss as _pl
 from ._abi import ptr as _ptr
+from ._pixel_loss import KINDS, PIXELS_PER_LANE, THREADS, FOLD, kind_code, CODE_DTYPES as _CODE_DTYPES  # noqa: F401 (this module's names too)
 
-KINDS = {"l1": 0, "charbonnier": 1}           # EX4D_DEPTH_L1, EX4D_DEPTH_CHARBONNIER
 ALIGNS = {"given": 0, "fit": 1}               # EX4D_DEPTH_ALIGN_*
 GT_U16, GT_F32 = 0, 1                         # EX4D_DEPTH_GT_*
 ROW = 6
-PIXELS_PER_LANE, THREADS, FOLD = 4, 256, 64   # EX4D_DEPTH_PIXELS_PER_LANE, EX4D_DEPTH_THREADS, EX4D_DEPTH_FOLD
-_CODE_DTYPES = (torch.uint16, torch.int16)
-
-
-def kind_code(kind):
-    if kind not in KINDS:
-        raise ValueError(f"unknown kind {kind!r}: one of {sorted(KINDS)}")
-    return KINDS[kind]
 
 
 def align_code(align):
@@ -64,8 +56,7 @@ def decode_invdepth(gt, code_scale=1.0):
 
 
 def _check(out_depth, gt, acc):
-    if not out_depth.is_cuda:
-        raise RuntimeError(f"out_depth is on {out_depth.device}: the depth loss kernels only run on a ROCm GPU (no CPU fallback)")
+    _pl.require_device(out_depth, "out_depth", "depth")
     if out_depth.dim() not in (2, 3) or (out_depth.dim() == 3 and out_depth.shape[0] != 1) or out_depth.dtype != torch.float32 \
             or not out_depth.is_contiguous():
         raise RuntimeError("out_depth must be a contiguous float32 [H,W] or [1,H,W] tensor (the rasterizer's depth output)")
@@ -73,8 +64,7 @@ def _check(out_depth, gt, acc):
     if (gt.dtype not in _CODE_DTYPES and gt.dtype != torch.float32) or gt.dim() != 2 or tuple(gt.shape) != (H, W) \
             or gt.device != out_depth.device or not gt.is_contiguous():
         raise RuntimeError("gt must be a contiguous torch.uint16, torch.int16 or torch.float32 [H,W] tensor on out_depth's device")
-    if acc is not None and (acc.dtype != torch.float32 or acc.numel() != H * W or acc.device != out_depth.device or not acc.is_contiguous()):
-        raise RuntimeError("acc must be a contiguous float32 [H,W] or [1,H,W] tensor on out_depth's device")
+    _pl.check_acc(acc, H, W, out_depth.device, "out_depth")
     return H, W
 
 
@@ -90,17 +80,8 @@ def depth_loss_raw(out_depth, gt, code_scale=1.0, align="fit", scale=1.0, offset
     code, how = kind_code(kind), align_code(align)
     H, W = _check(out_depth, gt, acc)
     dev = out_depth.device
-    if loss is None:
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-    if row is None:
-        row = torch.empty(ROW, dtype=torch.float64, device=dev)
-    elif row.dtype != torch.float64 or row.device != dev or row.numel() != ROW or not row.is_contiguous():
-        raise RuntimeError("row must be a contiguous float64 [6] tensor on out_depth's device")
     need = _abi.load().ex4d_depth_loss_scratch_bytes(H, W)
-    if scratch is None:
-        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
-    elif scratch.dtype != torch.uint8 or scratch.device != dev or scratch.numel() < need or not scratch.is_contiguous():
-        raise RuntimeError(f"scratch must be a contiguous uint8 tensor of at least {need} bytes on out_depth's device")
+    loss, row, scratch = _pl.forward_outputs(loss, row, scratch, ROW, need, torch.uint8, "bytes", dev, "out_depth")
     with _abi.stream(dev) as stream:
         _abi.call("ex4d_depth_loss_forward", H, W, out_depth.data_ptr(), gt.data_ptr(), gt_type(gt), float(code_scale), _ptr(acc), how,
                   float(scale), float(offset), code, float(eps), loss.data_ptr(), row.data_ptr(), scratch.data_ptr(), stream)
@@ -114,14 +95,9 @@ def depth_loss_backward_raw(out_depth, gt, row, grad_loss, code_scale=1.0, align
     code, how = kind_code(kind), align_code(align)
     H, W = _check(out_depth, gt, acc)
     dev = out_depth.device
-    if row.dtype != torch.float64 or row.device != dev or row.numel() != ROW or not row.is_contiguous():
-        raise RuntimeError("row must be a contiguous float64 [6] tensor on out_depth's device")
-    if grad_loss.dtype != torch.float32 or grad_loss.device != dev or grad_loss.numel() != 1:
-        raise RuntimeError("grad_loss must be a float32 tensor of one element on out_depth's device")
-    if out is None:
-        out = torch.empty_like(out_depth)
-    elif out.dtype != torch.float32 or out.device != dev or out.numel() != H * W or not out.is_contiguous():
-        raise RuntimeError("out must be a contiguous float32 [H,W] or [1,H,W] tensor on out_depth's device")
+    _pl.check_row(row, ROW, dev, "out_depth")
+    _pl.check_grad_loss(grad_loss, dev, "out_depth")
+    out = _pl.gradient_output(out, out_depth, lambda o: o.numel() == H * W, "[H,W] or [1,H,W]", "out_depth")
     with _abi.stream(dev) as stream:
         _abi.call("ex4d_depth_loss_backward", H, W, out_depth.data_ptr(), gt.data_ptr(), gt_type(gt), float(code_scale), _ptr(acc), how,
                   code, float(eps), row.data_ptr(), grad_loss.data_ptr(), out.data_ptr(), stream)
@@ -152,8 +128,7 @@ def depth_loss(out_depth, gt, code_scale=1.0, align="fit", scale=1.0, offset=0.0
     fit of align="fit" is detached)."""
     kind_code(kind)
     align_code(align)
-    if not out_depth.is_cuda:
-        raise RuntimeError(f"out_depth is on {out_depth.device}: the depth loss kernels only run on a ROCm GPU (no CPU fallback)")
+    _pl.require_device(out_depth, "out_depth", "depth")
     return _DepthLoss.apply(out_depth, gt, code_scale, align, scale, offset, kind, eps, acc)
 
 

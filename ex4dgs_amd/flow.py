@@ -20,19 +20,11 @@ read-back per set; `decode_flow` is the reference's decode in torch ops, CPU or 
 """
 import torch
 
-from . import _abi
+from . import _abi, _pixel_loss as _pl
 from ._abi import ptr as _ptr
+from ._pixel_loss import KINDS, PIXELS_PER_LANE, THREADS, FOLD, kind_code, CODE_DTYPES as _CODE_DTYPES  # noqa: F401 (this module's names too)
 
-KINDS = {"l1": 0, "charbonnier": 1}           # EX4D_FLOW_*
 ROW = 4
-PIXELS_PER_LANE, THREADS, FOLD = 4, 256, 64   # EX4D_FLOW_PIXELS_PER_LANE, EX4D_FLOW_THREADS, EX4D_FLOW_FOLD
-_CODE_DTYPES = (torch.uint16, torch.int16)
-
-
-def kind_code(kind):
-    if kind not in KINDS:
-        raise ValueError(f"unknown kind {kind!r}: one of {sorted(KINDS)}")
-    return KINDS[kind]
 
 
 def _words(encoded):
@@ -54,16 +46,14 @@ def decode_flow(encoded, flow_scale=1.0):
 
 
 def _check(out_flow, encoded, acc):
-    if not out_flow.is_cuda:
-        raise RuntimeError(f"out_flow is on {out_flow.device}: the flow loss kernels only run on a ROCm GPU (no CPU fallback)")
+    _pl.require_device(out_flow, "out_flow", "flow")
     if out_flow.dim() != 3 or out_flow.shape[0] != 3 or out_flow.dtype != torch.float32 or not out_flow.is_contiguous():
         raise RuntimeError("out_flow must be a contiguous float32 [3,H,W] tensor (the rasterizer's opticalflow output)")
     H, W = int(out_flow.shape[1]), int(out_flow.shape[2])
     if encoded.dtype not in _CODE_DTYPES or encoded.dim() != 3 or encoded.shape[2] not in (3, 4) or tuple(encoded.shape[:2]) != (H, W) \
             or encoded.device != out_flow.device or not encoded.is_contiguous():
         raise RuntimeError("encoded flow must be a contiguous torch.uint16 or torch.int16 [H,W,3|4] tensor on out_flow's device")
-    if acc is not None and (acc.dtype != torch.float32 or acc.numel() != H * W or acc.device != out_flow.device or not acc.is_contiguous()):
-        raise RuntimeError("acc must be a contiguous float32 [H,W] or [1,H,W] tensor on out_flow's device")
+    _pl.check_acc(acc, H, W, out_flow.device, "out_flow")
     return H, W
 
 
@@ -77,17 +67,8 @@ def flow_loss_raw(out_flow, encoded, flow_scale=1.0, kind="charbonnier", eps=1e-
     code = kind_code(kind)
     H, W = _check(out_flow, encoded, acc)
     dev = out_flow.device
-    if loss is None:
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-    if row is None:
-        row = torch.empty(ROW, dtype=torch.float64, device=dev)
-    elif row.dtype != torch.float64 or row.device != dev or row.numel() != ROW or not row.is_contiguous():
-        raise RuntimeError("row must be a contiguous float64 [4] tensor on out_flow's device")
     need = _abi.load().ex4d_flow_loss_scratch_floats(H, W)
-    if scratch is None:
-        scratch = torch.empty(need, dtype=torch.float32, device=dev)
-    elif scratch.dtype != torch.float32 or scratch.device != dev or scratch.numel() < need or not scratch.is_contiguous():
-        raise RuntimeError(f"scratch must be a contiguous float32 tensor of at least {need} elements on out_flow's device")
+    loss, row, scratch = _pl.forward_outputs(loss, row, scratch, ROW, need, torch.float32, "elements", dev, "out_flow")
     with _abi.stream(dev) as stream:
         _abi.call("ex4d_flow_loss_forward", H, W, out_flow.data_ptr(), encoded.data_ptr(), int(encoded.shape[2]), float(flow_scale),
                   _ptr(acc), code, float(eps), loss.data_ptr(), row.data_ptr(), scratch.data_ptr(), stream)
@@ -100,14 +81,9 @@ def flow_loss_backward_raw(out_flow, encoded, row, grad_loss, flow_scale=1.0, ki
     code = kind_code(kind)
     H, W = _check(out_flow, encoded, acc)
     dev = out_flow.device
-    if row.dtype != torch.float64 or row.device != dev or row.numel() != ROW or not row.is_contiguous():
-        raise RuntimeError("row must be a contiguous float64 [4] tensor on out_flow's device")
-    if grad_loss.dtype != torch.float32 or grad_loss.device != dev or grad_loss.numel() != 1:
-        raise RuntimeError("grad_loss must be a float32 tensor of one element on out_flow's device")
-    if out is None:
-        out = torch.empty_like(out_flow)
-    elif out.dtype != torch.float32 or out.device != dev or tuple(out.shape) != (3, H, W) or not out.is_contiguous():
-        raise RuntimeError("out must be a contiguous float32 [3,H,W] tensor on out_flow's device")
+    _pl.check_row(row, ROW, dev, "out_flow")
+    _pl.check_grad_loss(grad_loss, dev, "out_flow")
+    out = _pl.gradient_output(out, out_flow, lambda o: tuple(o.shape) == (3, H, W), "[3,H,W]", "out_flow")
     with _abi.stream(dev) as stream:
         _abi.call("ex4d_flow_loss_backward", H, W, out_flow.data_ptr(), encoded.data_ptr(), int(encoded.shape[2]), float(flow_scale),
                   _ptr(acc), code, float(eps), row.data_ptr(), grad_loss.data_ptr(), out.data_ptr(), stream)
@@ -136,8 +112,7 @@ def flow_loss(out_flow, encoded, flow_scale=1.0, kind="charbonnier", eps=1e-3, a
     """The scalar loss of the module docstring for a rendered [3,H,W] flow and its encoded ground truth; differentiable in `out_flow`
     only (`acc`, the rasterizer's [1,H,W] or [H,W] accumulated alpha, weighs the pixels as a constant)."""
     kind_code(kind)
-    if not out_flow.is_cuda:
-        raise RuntimeError(f"out_flow is on {out_flow.device}: the flow loss kernels only run on a ROCm GPU (no CPU fallback)")
+    _pl.require_device(out_flow, "out_flow", "flow")
     return _FlowLoss.apply(out_flow, encoded, flow_scale, kind, eps, acc)
 
 

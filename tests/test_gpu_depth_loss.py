@@ -14,7 +14,7 @@ import torch
 
 from tests import depth_ref as dr
 from tests import helpers as h
-from tests.test_gpu_flow import DEV, _bits, _poisoned          # the poison and bit-comparison helpers of the flow tests
+from tests.pixel_loss_helpers import DEV, bits as _bits, close as _close, poisoned as _poisoned
 
 pytestmark = pytest.mark.gpu
 TABLE = [(n, k, al, a, gt) for n in dr.CASES for k in dr.KINDS for al in dr.ALIGNS for a in (False, True) for gt in dr.GT_TYPES]
@@ -49,14 +49,6 @@ def _backward(c, depth, gt, acc, kind, align, row, out=None, grad_loss=dr.GRAD_L
     g = torch.full((1,), grad_loss, device=DEV)
     return _xdepth().depth_loss_backward_raw(depth, gt, row, g, c["code_scale"], align, kind, dr.EPS, acc,
                                              out=_poisoned(c["H"], c["W"]) if out is None else out)
-
-
-def _close(got, ref):
-    """|got - ref| / |ref|; a reference of exactly 0 has to be met exactly."""
-    if ref == 0.0:
-        assert got == 0.0, got
-        return 0.0
-    return abs(got - ref) / abs(ref)
 
 
 def _same(a, b):

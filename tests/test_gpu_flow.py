@@ -13,21 +13,12 @@ import torch
 
 from tests import flow_ref as fr
 from tests import helpers as h
+from tests.pixel_loss_helpers import DEV, bits as _bits, close as _close, poisoned as _poisoned
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 TABLE = [(n, k, a, s) for n in fr.CASES for k in fr.KINDS for a in (False, True) for s in (3, 4)]
 IDS = [f"{n}-{k}-{'acc' if a else 'noacc'}-s{s}" for n, k, a, s in TABLE]
 WORST = {"forward": 0.0, "backward": 0.0}
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int64)
-
-
-def _poisoned(*shape, dtype=torch.float32):
-    words = torch.full(shape, -1, dtype=torch.int32 if dtype == torch.float32 else torch.int64, device=DEV)          # 0xFF bytes
-    return words.view(dtype)
 
 
 def _inputs(name, S, use_acc, dtype="int16", word_offset=0):
@@ -49,14 +40,6 @@ def _forward(xflow, c, flow, enc, acc, kind):
 def _backward(xflow, c, flow, enc, acc, kind, row, out=None):
     g = torch.full((1,), fr.GRAD_LOSS, device=DEV)
     return xflow.flow_loss_backward_raw(flow, enc, row, g, c["scale"], kind, fr.EPS, acc, out=_poisoned(3, c["H"], c["W"]) if out is None else out)
-
-
-def _close(got, ref):
-    """|got - ref| / |ref|; a reference of exactly 0 has to be met exactly."""
-    if ref == 0.0:
-        assert got == 0.0, got
-        return 0.0
-    return abs(got - ref) / abs(ref)
 
 
 # ---------------------------------------------------------------------------------------------- 1, 2: the kernels on the case table
